@@ -9,6 +9,12 @@ Launch (one process per GPU; the reference is single-device, attributions.py:16-
   + ``TORCHPRUNER_DIST_BACKEND=gloo`` rehearses N ranks on one GPU).
 * The JSON reports ``dist_backend`` and ``world_size_seen`` (``dist.get_world_size()``).
 
+A plain run (``python bench.py --gpus N --steps K --warmup W``) does only what the headline
+needs: teacher, W warm-up steps, K timed steps, the JSON line (``ms_per_step``: one timed step;
+``vs_baseline`` null). ``--dump-outputs DIR`` also writes the timed run's scores as ``.npy``.
+``--full`` adds everything below that is not the headline: ``vs_baseline`` and
+``generic_run_many_img_s``, the other BASELINE configs and the accuracy protocol.
+
 Throughput (timed; BASELINE.json config #2, scaled to N GPUs):
 * VGG16-BN / CIFAR-10 shape (reference experiments/models/cifar10.py:62-77), eval mode, fp32
   (the reference's precision), weights of a briefly trained teacher (untimed). Every rank
@@ -30,7 +36,7 @@ Throughput (timed; BASELINE.json config #2, scaled to N GPUs):
   module/hook path with MIOpen / hipBLASLt convolutions (``TORCHPRUNER_ENGINES=0``,
   ``TORCHPRUNER_GENERIC_NATIVE=0``), sharded the same way.
 
-Other BASELINE configs in the same run (all ranks, sharded like the headline):
+Other BASELINE configs in the same run (``--full``; all ranks, sharded like the headline):
 * ``resnet50_apoz_img_s`` / ``resnet50_taylor_img_s``: config #3, ResNet-50 224x224 B=256 per
   GPU, every prunable bottleneck conv in one ``run_many`` on the ResNet engine.
 * ``vgg_taylor_b100_img_s``: the headline's fp32 Taylor run_many at the reference's attribution
@@ -44,7 +50,7 @@ Other BASELINE configs in the same run (all ranks, sharded like the headline):
   conv + DDP rewrap; ``resnet50_prune_finetune``: one prune -> finetune round, Taylor vs Random,
   from one teacher (``bench/resnet_finetune.py``).
 
-Accuracy (untimed; ``bench/prune_quality.py``, rank 0 after the process group is torn down):
+Accuracy (``--full``; untimed; ``bench/prune_quality.py``, rank 0 after the process group is torn down):
 the teacher is pruned for real — ``Pruner.prune_model`` through ``get_vgg_pruning_graph`` on
 every conv, 50% of the filters, in 4 increments per layer with a few SGD steps between
 increments (Molchanov-style iterative pruning), Taylor scores vs Random scores under the same
@@ -79,6 +85,14 @@ def parse():
                     help="images per GPU per step (HBM-sized: small-spatial layers need >= 2k images to "
                          "fill 256 CUs; 4096 / 8192 measure 1-3%% more, but the MIOpen comparison extra "
                          "then re-tunes for a minute)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this file measures: the reference-semantics "
+                         "eager timing (vs_baseline), the extras and the accuracy protocol (each can be switched "
+                         "off again with --no-baseline / --no-extras / --extras / --no-prune). Without --full "
+                         "only the headline is set up, warmed up, timed and reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the timed run_many returned (one float32 score "
+                         "vector per conv layer, covering the timed steps up to the last) as DIR/<name>.npy")
     ap.add_argument("--no-baseline", action="store_true", help="skip the reference-semantics eager timing")
     ap.add_argument("--baseline-batches", type=int, default=2)
     ap.add_argument("--no-prune", action="store_true", help="skip the (untimed) accuracy protocol")
@@ -218,6 +232,8 @@ def run(args) -> int:
     del warm, metric
     phase["headline"] = time.perf_counter() - t0
     head_choices = tuner_choices()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, scores)
     value = args.steps * B * world / dt
     log(f"[bench] {world} GPU(s) x {args.steps} steps x B={B}: {dt * 1e3:.1f} ms -> {value:.0f} img/s "
         f"(fused path, backend {backend_seen}, world {world_seen})")
@@ -255,7 +271,7 @@ def run(args) -> int:
         "phase_wall_s": phase,
     }
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # the extras run after the timed headline: one that raises (on every rank alike) is reported in
         # the JSON line instead of costing the headline its line
         try:
@@ -272,7 +288,7 @@ def run(args) -> int:
     if rank != 0:
         return 0
 
-    if not args.no_baseline:
+    if args.full and not args.no_baseline:
         from torchpruner_amd.bench.reference_semantics import reference_taylor_all
         from torchpruner_amd.data import DeviceLoader
         nb = args.baseline_batches
@@ -302,7 +318,7 @@ def run(args) -> int:
             log(f"[bench] reference-semantics eager: {eager:.0f} img/s per GPU -> vs_baseline {result['vs_baseline']}")
         phase["eager_reference"] = time.perf_counter() - t_eager
 
-    if not args.no_prune:
+    if args.full and not args.no_prune:
         t0 = time.perf_counter()
         try:
             result.update(accuracy(args, model, task, convs, scores, cfg, dev, log))
@@ -315,6 +331,19 @@ def run(args) -> int:
 
     print(json.dumps(result), flush=True)
     return 0
+
+
+def dump_outputs(out_dir, scores):
+    """``--dump-outputs``: what the timed ``run_many`` returned to its caller, one array per conv
+    layer in network order (``taylor_conv00.npy`` ...): each the layer's per-filter Taylor scores
+    over every timed step, the last included (all-reduced over the ranks). The batches come from
+    ``--seed`` alone, so two builds run with the same arguments score the same images."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, s in enumerate(scores):
+        s = np.asarray(s)
+        np.save(os.path.join(out_dir, f"taylor_conv{k:02d}.npy"),
+                s if s.dtype in (np.float32, np.float64) else s.astype(np.float64))
 
 
 def extras(args, model, task, convs, dev, world, rank, timed_run, log, value, phase, scores):

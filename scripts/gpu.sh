@@ -5,7 +5,7 @@
 #
 # tasks
 #   tests [pytest -k expr]  GPU suite (one process, per-test timeout), then smoke()
-#   bench [bench args]      the driver's bench line (default: --steps 20 --warmup 5) -> gpurun_out/bench.json
+#   bench [bench args]      the whole bench line (default: --full --steps 20 --warmup 5) -> bench.json in the output folder
 #   headline-prof           headline step: tuner log + kernel trace with one / two batches in flight
 #   train-prof [rounds]     ResNet-50 training step (dense / pruned rounds) + kernel trace of the last round
 #   resnet-prof             ResNet-50 APoZ / Taylor engine step kernel traces (B=256)
@@ -49,7 +49,7 @@ case $task in
     tail -1 "$O/smoke.log"
     ;;
   bench)
-    args=${*:-"--steps 20 --warmup 5"}
+    args=${*:-"--full --steps 20 --warmup 5"}
     timeout -k 10 900 python -u bench.py $args > "$O/bench.json" 2> "$O/bench.err" || { tail -30 "$O/bench.err"; exit 1; }
     grep "\[bench\]" "$O/bench.err"
     ;;
@@ -108,7 +108,7 @@ case $task in
     ;;
   dist)
     N=${1:-4}
-    TORCHPRUNER_DIST_BACKEND=gloo TORCHPRUNER_SHARE_GPU=1 step dist$N 1000 python -u bench.py --gpus "$N" --steps 2 --warmup 1 \
+    TORCHPRUNER_DIST_BACKEND=gloo TORCHPRUNER_SHARE_GPU=1 step dist$N 1000 python -u bench.py --gpus "$N" --full --steps 2 --warmup 1 \
       --batch 128 --teacher-steps 50 --baseline-batches 1 --quality-seeds 1 --generic-steps 1 --resnet-steps 1 --resnet-batch 16 \
       --finetune-steps 1 --finetune-batch 8 --finetune-res 64 --q5-res 64 --q5-max-steps 25
     grep "\[bench\]" "$O/dist$N.log"
@@ -124,7 +124,7 @@ case $task in
     grep ddp_overlap "$O/ddp_overlap.log"
     ;;
   b100)
-    TORCHPRUNER_TUNER_LOG=1 step b100 400 python -u bench.py --steps 2 --warmup 1 --teacher-steps 0 --no-prune --no-baseline --extras b100
+    TORCHPRUNER_TUNER_LOG=1 step b100 400 python -u bench.py --full --steps 2 --warmup 1 --teacher-steps 0 --no-prune --no-baseline --extras b100
     grep "\[bench\]" "$O/b100.log"
     ;;
   *)

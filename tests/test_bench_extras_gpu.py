@@ -22,7 +22,8 @@ def test_bench_pruned_extra(cuda):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONUNBUFFERED"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch",
-                        "128", "--teacher-steps", "20", "--no-baseline", "--no-prune", "--extras", "pruned"],
+                        "128", "--teacher-steps", "20", "--full", "--no-baseline", "--no-prune", "--extras",
+                        "pruned"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
