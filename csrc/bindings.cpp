@@ -327,6 +327,91 @@ at::Tensor maxpool_train_bwd(const at::Tensor& g_, const at::Tensor& am, int64_t
   return dx;
 }
 
+// Depthwise convolution (depth multiplier 1) on NHWC: x (B, H, W, C), w the (C, 1, k, k) parameter
+// read in place, k in {3, 5}, stride in {1, 2}, zero padding 0..k-1, any C.
+void check_dw_geometry(int64_t H, int64_t W, int64_t k, int64_t s, int64_t pad) {
+  TORCH_CHECK((k == 3 || k == 5) && (s == 1 || s == 2) && pad >= 0 && pad <= k - 1 && H + 2 * pad >= k &&
+                  W + 2 * pad >= k, "bad depthwise conv geometry: k ", k, " stride ", s, " pad ", pad, " on ", H, "x", W);
+}
+
+void check_dw_weight(const at::Tensor& w, int64_t C, const at::Tensor& like) {
+  check_cuda_f32(w, "w");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == w.size(3) && w.is_contiguous() &&
+                  w.device() == like.device(), "w must be a contiguous (C, 1, k, k) depthwise weight");
+}
+
+at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t s,
+                      int64_t pad) {
+  check_cuda_f32(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "x must be a non-empty contiguous NHWC tensor");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  check_dw_weight(w, C, x);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  TORCH_CHECK(x.numel() < (int64_t(1) << 29), "x exceeds the kernels' 2 GiB operand range");
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    check_cuda_f32(*bias, "bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == C && bias->is_contiguous() && bias->device() == x.device(),
+                "bias must be a contiguous (C,) tensor");
+    bp = bias->data_ptr<float>();
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty({B, (H + 2 * pad - k) / s + 1, (W + 2 * pad - k) / s + 1, C}, x.options());
+  TP_CHECK_HIP(tp_dwconv_fwd(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)B, (int)H,
+                             (int)W, (int)C, (int)k, (int)s, (int)pad, cur_stream()));
+  return y;
+}
+
+at::Tensor dwconv_dgrad(const at::Tensor& g_, const at::Tensor& w, int64_t H, int64_t W, int64_t s, int64_t pad) {
+  check_cuda_f32(g_, "g");
+  auto g = g_.contiguous();
+  TORCH_CHECK(g.dim() == 4 && g.numel() > 0 && H > 0 && W > 0, "g must be a non-empty (B, Ho, Wo, C) tensor");
+  const int64_t B = g.size(0), C = g.size(3);
+  check_dw_weight(w, C, g);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  TORCH_CHECK(g.size(1) == (H + 2 * pad - k) / s + 1 && g.size(2) == (W + 2 * pad - k) / s + 1, "g shape mismatch");
+  TORCH_CHECK(H < (int64_t(1) << 29) && W < (int64_t(1) << 29) && B * H * W * C < (int64_t(1) << 29),
+              "dx exceeds the kernels' 2 GiB operand range");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  auto dx = at::empty({B, H, W, C}, g.options());
+  TP_CHECK_HIP(tp_dwconv_dgrad(g.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H,
+                               (int)W, (int)C, (int)k, (int)s, (int)pad, cur_stream()));
+  return dx;
+}
+
+// dW is written into ``dw`` with that tensor's own strides (the parameter's: DDP bucket views);
+// returns the bias gradient (C,) when asked for.
+c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x, int64_t k, int64_t s, int64_t pad,
+                                       at::Tensor& dw, bool want_bias) {
+  check_cuda_f32(g_, "g");
+  check_cuda_f32(x, "x");
+  check_cuda_f32(dw, "dw");
+  auto g = g_.contiguous();
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && g.dim() == 4 && g.numel() > 0 && x.device() == g.device(),
+              "g / x must be non-empty contiguous NHWC tensors on one device");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  check_dw_geometry(H, W, k, s, pad);
+  const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+  TORCH_CHECK(g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo && g.size(3) == C, "g shape mismatch");
+  TORCH_CHECK(dw.dim() == 4 && dw.size(0) == C && dw.size(1) == 1 && dw.size(2) == k && dw.size(3) == k &&
+                  dw.device() == g.device() && dw.stride(0) > 0 && dw.stride(2) > 0 && dw.stride(3) > 0,
+              "dw must be a (C, 1, k, k) tensor with positive strides");
+  TORCH_CHECK(x.numel() < (int64_t(1) << 29) && g.numel() < (int64_t(1) << 29),
+              "g / x exceed the kernels' 2 GiB operand range");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  const int chunks = tp_dwconv_wgrad_chunks((int)(B * Ho * Wo), (int)C);
+  auto ws = at::empty({(int64_t)chunks * (k * k + 1) * C}, g.options().dtype(at::kDouble));
+  c10::optional<at::Tensor> db;
+  if (want_bias) db = at::empty({C}, g.options());
+  TP_CHECK_HIP(tp_dwconv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
+                               want_bias ? db->data_ptr<float>() : nullptr, ws.data_ptr<double>(), chunks, (int)B,
+                               (int)H, (int)W, (int)C, (int)k, (int)s, (int)pad, dw.stride(0), dw.stride(2),
+                               dw.stride(3), cur_stream()));
+  return db;
+}
+
 at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
   check_cuda_f32(g_, "g");
   auto g = g_.contiguous();
@@ -356,6 +441,9 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("maxpool_train_fwd(Tensor x, int k, int s, int pad) -> (Tensor, Tensor)");
   m.def("maxpool_train_bwd(Tensor g, Tensor am, int H, int W, int k, int s, int pad) -> Tensor");
   m.def("avgpool_bwd(Tensor g, int H, int W) -> Tensor");
+  m.def("dwconv_fwd(Tensor x, Tensor w, Tensor? bias, int stride, int pad) -> Tensor");
+  m.def("dwconv_dgrad(Tensor g, Tensor w, int H, int W, int stride, int pad) -> Tensor");
+  m.def("dwconv_wgrad(Tensor g, Tensor x, int k, int stride, int pad, Tensor(a!) dw, bool want_bias) -> Tensor?");
   register_engine_ops_def(m);
 }
 
@@ -375,5 +463,8 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("maxpool_train_fwd", &maxpool_train_fwd);
   m.impl("maxpool_train_bwd", &maxpool_train_bwd);
   m.impl("avgpool_bwd", &avgpool_bwd);
+  m.impl("dwconv_fwd", &dwconv_fwd);
+  m.impl("dwconv_dgrad", &dwconv_dgrad);
+  m.impl("dwconv_wgrad", &dwconv_wgrad);
   register_engine_ops_impl(m);
 }

@@ -16,7 +16,8 @@ from .attributions import (
     WeightNormAttributionMetric,
 )
 from .pruner import OptimizerPruner, Pruner
-from .utils import find_best_module_for_attributions, get_resnet_pruning_graph, get_vgg_pruning_graph
+from .utils import (find_best_module_for_attributions, get_mobilenet_pruning_graph, get_resnet_pruning_graph,
+                    get_vgg_pruning_graph)
 
 __all__ = [
     "APoZAttributionMetric",
@@ -28,6 +29,7 @@ __all__ = [
     "OptimizerPruner",
     "Pruner",
     "find_best_module_for_attributions",
+    "get_mobilenet_pruning_graph",
     "get_resnet_pruning_graph",
     "get_vgg_pruning_graph",
 ]

@@ -268,8 +268,9 @@ class _AttributionMetric(ABC):
         reasons = [r for r in dict.fromkeys(why or ())]
         self.last_path = {"path": path, "modules": mods, "reasons": reasons}
         if path.startswith("generic") and torch.device(self.device).type == "cuda":
-            from ..engine.train import eligible
-            self.last_path["native_convs"] = sum(eligible(m) for m in self.model.modules()) \
+            from ..engine import train as _t
+            self.last_path["native_convs"] = sum(_t.eligible(m) or (_t._NATIVE_DW and _t.dw_eligible(m))
+                                                 for m in self.model.modules()) \
                 if os.environ.get("TORCHPRUNER_GENERIC_NATIVE", "1") != "0" and not self._reduced_precision() else 0
         msg = f"{type(self).__name__}: {path} path for {', '.join(mods)}"
         if reasons:

@@ -80,12 +80,16 @@ class ShapleyAttributionMetric(_AttributionMetric):
         if fused is not None:
             self._record_path(path, [module], why)
             return self._run_batches(module, sv_samples, fused)
-        if hasattr(self.model, "forward_partial"):
+        # a model whose forward_partial only starts / stops at some of its modules says which
+        # (``is_partial_stage``): a module nested inside a residual block takes the hook path
+        is_stage = getattr(self.model, "is_partial_stage", None)
+        if hasattr(self.model, "forward_partial") and (is_stage is None or is_stage(module)):
             self._record_path("generic-partial", [module], why)
             return self.run_module_with_partial(module, sv_samples)
         self._record_path("generic-hook", [module], why)
-        logger.warning("Consider adding a 'forward_partial' method to your model to speed-up Shapley values "
-                       "computation")
+        if not hasattr(self.model, "forward_partial"):
+            logger.warning("Consider adding a 'forward_partial' method to your model to speed-up Shapley values "
+                           "computation")
         return self.run_module(module, sv_samples)
 
     # ------------------------------------------------------------------ helpers

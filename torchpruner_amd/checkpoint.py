@@ -68,6 +68,9 @@ def shrink_to_state_dict(model: nn.Module, state_dict: dict, manifest: Optional[
         if isinstance(m, _ConvNd):
             w = m.weight
             transposed = isinstance(m, _ConvTransposeNd)
+            if (not transposed and m.groups != 1 and m.groups == m.in_channels == m.out_channels
+                    and w.shape[1] == 1):
+                m.groups = w.shape[0]  # a depthwise conv stays depthwise at the checkpoint's width
             m.out_channels = w.shape[1] * m.groups if transposed else w.shape[0]
             m.in_channels = w.shape[0] if transposed else w.shape[1] * m.groups
         elif isinstance(m, nn.Linear):

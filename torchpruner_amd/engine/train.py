@@ -14,6 +14,11 @@ convolutions of a model run on the precompiled gfx950 kernels instead, through a
             stride-1 3x3 also Winograd F(2x2,3x3) (``tpamd.wino_wgrad``: 16 batched GEMMs over the
             transformed tiles, 2.25x fewer multiplies), picked per shape by the tuner
 
+Depthwise convolutions (depth multiplier 1, 3x3 / 5x5, stride 1 / 2, any width) run on NHWC stencil
+kernels (``tpamd.dwconv_fwd`` / ``dwconv_dgrad`` / ``dwconv_wgrad``): memory-bound, no MFMA, no
+tuner, the weights read from the parameter in place; every prune round of a MobileNet changes the
+width of every one of them, which on the library path is a new shape to compile each time.
+
 Training-mode ``BatchNorm2d`` runs on deterministic NHWC batch-statistics / normalisation /
 backward kernels (K5, ``tpamd.bn_train_*``), training-mode ``nn.Dropout`` on a counter-based
 Philox kernel (K7b, mask regenerated in the backward), max-pool (argmax byte + gather backward)
@@ -84,6 +89,24 @@ def eligible(conv: nn.Module) -> bool:
     return k[0] in (1, 3)
 
 
+def dw_eligible(conv: nn.Module) -> bool:
+    """Whether ``conv`` is a depthwise convolution the native stencil kernels run
+    (``tpamd.dwconv_*``): depth multiplier 1 (groups == in_channels == out_channels), square 3x3 /
+    5x5, equal strides 1 or 2, equal zero padding up to ks-1, no dilation. Every other grouped
+    conv stays on the library path (:func:`eligible` keeps its meaning: the dense-GEMM convs)."""
+    if not isinstance(conv, nn.Conv2d) or conv.dilation != (1, 1):
+        return False
+    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        return False
+    w = conv.weight
+    if w.dim() != 4 or w.shape[1] != 1 or not (conv.groups == conv.in_channels == conv.out_channels == w.shape[0]):
+        return False
+    k, s, p = conv.kernel_size, conv.stride, conv.padding
+    if k[0] != k[1] or s[0] != s[1] or p[0] != p[1] or p[0] > k[0] - 1:
+        return False
+    return k[0] in (3, 5) and s[0] in (1, 2)
+
+
 def _act_w(c: int) -> int:
     """Channel width a native activation carries: the next multiple of 8 (the F(4x4) kernel's input
     granule; the implicit GEMMs take any multiple of 4, BN any width). A 20 %-pruned ResNet-50
@@ -141,6 +164,10 @@ _BWD_FUSE = os.environ.get("TORCHPRUNER_BN_BWD_FUSE", "1") != "0"
 # backward passes that took each fusion (tests / diagnostics): tail statistics from a dgrad epilogue,
 # identity gradients handed over unmasked
 FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0}
+# TORCHPRUNER_NATIVE_DW=0: depthwise convs stay on the library path (A/B switch, read once)
+_NATIVE_DW = os.environ.get("TORCHPRUNER_NATIVE_DW", "1") != "0"
+# launches of the depthwise kernels (tests / diagnostics)
+DW_COUNTS = {"fwd": 0, "dgrad": 0, "wgrad": 0}
 
 
 class _BNLink:
@@ -952,6 +979,68 @@ def _fits(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return B * H * W * cin_p * 4 <= _MAX_BYTES and B * Ho * Wo * cout_p * 4 <= _MAX_BYTES and Ho > 0 and Wo > 0
 
 
+class _NativeDWConv2d(torch.autograd.Function):
+    """Depthwise conv (depth multiplier 1) on the NHWC stencil kernels: the weight is read from
+    the parameter in place (no pack), the gradients are deterministic gathers / ordered sums. The
+    channel count is the weight tensor's, not the module's metadata."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad):
+        xh = _nhwc(x)  # no copy for a channels_last input
+        w = weight.detach()
+        if not w.is_contiguous():
+            w = w.contiguous()
+        y = ops.require().dwconv_fwd(xh, w, bias.detach() if bias is not None else None, stride, pad)
+        DW_COUNTS["fwd"] += 1
+        ctx.save_for_backward(xh, w)
+        ctx.geom = (stride, pad, weight.stride(), bias is not None)
+        return _as_nchw(y)
+
+    @staticmethod
+    def backward(ctx, gy):
+        T = ops.require()
+        xh, w = ctx.saved_tensors
+        stride, pad, w_strides, has_bias = ctx.geom
+        g = _nhwc(gy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _as_nchw(T.dwconv_dgrad(g, w, xh.shape[1], xh.shape[2], stride, pad))
+            DW_COUNTS["dgrad"] += 1
+        want_b = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            # dW in the parameter's exact strides (the _conv_wgrad contract: DDP bucket views)
+            dw = torch.empty_strided(tuple(w.shape), w_strides, dtype=torch.float32, device=g.device)
+            db = T.dwconv_wgrad(g, xh, w.shape[2], stride, pad, dw, want_b)
+            DW_COUNTS["wgrad"] += 1
+            if not ctx.needs_input_grad[1]:
+                dw = None
+        return dx, dw, db, None, None
+
+
+def _dw_fits(w: torch.Tensor, x: torch.Tensor, ks: int, s: int, p: int) -> bool:
+    B, C, H, W = x.shape
+    Ho, Wo = (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1
+    if not (C == w.shape[0] and B > 0 and H + 2 * p >= ks and W + 2 * p >= ks
+            and B * H * W * C * 4 <= _MAX_BYTES and B * Ho * Wo * C * 4 <= _MAX_BYTES):
+        return False
+    # the launchers' grid limit (2^24 blocks): one block per 256 (4-column strip, channel vector)
+    # pairs of an image row (forward: output rows, dgrad: input rows), 16 (tap, channel) pairs in the fold
+    cv = C // 4 if C % 4 == 0 else C
+    blocks = max(B * Ho * -(-(-(-Wo // 4) * cv) // 256), B * H * -(-(-(-W // 4) * cv) // 256), (ks * ks + 1) * C // 16 + 1)
+    return blocks < (1 << 24)
+
+
+def _native_dw_forward(self, x):
+    """Depthwise ``nn.Conv2d.forward`` on the native kernels. (A different function from
+    :func:`_native_forward`: containers that carry padded activations between dense convs hand a
+    depthwise conv the real-width slice, like any other module.)"""
+    ks, s, p = _geom(self)
+    if not x.is_cuda or x.dtype != torch.float32 or self.weight.dtype != torch.float32 or x.dim() != 4 \
+            or not _dw_fits(self.weight, x, ks, s, p):
+        return type(self).forward(self, x)  # other dtypes / tensors beyond 2 GiB: the library path
+    return _NativeDWConv2d.apply(x, self.weight, self.bias, s, p)
+
+
 class _NativeDropout(torch.autograd.Function):
     """Training-mode inverted dropout on the Philox kernel (K7b): the mask is regenerated from
     (seed, element index) in the backward, nothing is stored."""
@@ -1011,7 +1100,9 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
     training mode — the fused BN / ReLU modules (and the convs run by a block's entry node or with
     epilogue BN statistics: a bottleneck's conv1 / downsample, every block's conv2 / conv3, the
     stem conv) are then not called, so forward hooks on them do not fire (attribution passes use
-    ``fuse=False``, eval-mode forwards are unchanged). Also switched: ``nn.Linear`` (MFMA GEMM), ``nn.MaxPool2d``,
+    ``fuse=False``, eval-mode forwards are unchanged). Also switched: depthwise convs
+    (:func:`dw_eligible`, the NHWC stencil kernels; ``TORCHPRUNER_NATIVE_DW=0`` leaves them on the
+    library path), ``nn.Linear`` (MFMA GEMM), ``nn.MaxPool2d``,
     ``nn.AdaptiveAvgPool2d`` and, with ``dropout``, training-mode ``nn.Dropout`` (Philox masks
     seeded from torch's CPU RNG: a different random stream than PyTorch's dropout). Returns the
     switched modules; undo with :func:`disable_native_convs`."""
@@ -1036,6 +1127,9 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
             switched.append(m)
         elif eligible(m):
             m.forward = types.MethodType(_native_forward, m)
+            switched.append(m)
+        elif _NATIVE_DW and dw_eligible(m):
+            m.forward = types.MethodType(_native_dw_forward, m)
             switched.append(m)
         elif dropout and type(m) is nn.Dropout:
             m.forward = types.MethodType(_native_dropout_forward, m)

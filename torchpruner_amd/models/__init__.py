@@ -3,8 +3,10 @@ from .partial import PartialForwardMixin, SequentialPartial, run_stages, with_fo
 from .vgg import VGG, get_vgg_model_with_name, make_features, prunable_vgg16, vgg_cifar
 from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet34, resnet50, resnet101, resnet152
 from .mlp import FCNet, FMNISTConvNet, cifar10_fc, mnist_fc
+from .mobilenet import InvertedResidual, MobileNetV2, mobilenet_v2
 
 __all__ = [
+    "InvertedResidual", "MobileNetV2", "mobilenet_v2",
     "PartialForwardMixin", "SequentialPartial", "run_stages", "with_forward_partial",
     "VGG", "get_vgg_model_with_name", "make_features", "prunable_vgg16", "vgg_cifar",
     "ResNet", "BasicBlock", "Bottleneck", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",

@@ -12,8 +12,10 @@ Differences (deliberate fixes):
   optimizer state of matching shape (SGD momentum, Adam moments, ...) in *every* param group —
   is sliced by ONE multi-tensor HIP gather launch (ops.gather_multi) on GPU;
 * module metadata (``in_features``, ``out_channels``, ``num_features``...) is updated;
-* ``_DropoutNd`` (Dropout2d etc.) is accepted; grouped convolutions are rejected explicitly;
-  transposed convolutions are pruned on their correct weight axes;
+* ``_DropoutNd`` (Dropout2d etc.) is accepted; a depthwise convolution (depth multiplier 1) is
+  accepted as a cascading module (its channel c goes with channel c of its producer), every other
+  grouped convolution is rejected explicitly, and a cascade is validated before anything is
+  sliced; transposed convolutions are pruned on their correct weight axes;
 * in a live process group the pruning indices are broadcast from rank 0 (R5) so every
   data-parallel replica prunes identically.
 """
@@ -83,12 +85,16 @@ class Pruner:
             for h in handles:
                 h.remove()
 
-        # 2. Prune every cascading module whose input saw NaNs (inputs), then the module (outputs)
-        for next_module in cascading_modules:
-            idx = probe.nan_indices.get(next_module)
-            if idx is not None:
-                self._prune_module(next_module, _as_index_array(idx), direction="in",
-                                   original_len=probe.activation_len.get(next_module))
+        # 2. Prune every cascading module whose input saw NaNs (inputs), then the module (outputs).
+        # Every cut is validated before the first one is made: a rejected cascade (an unsupported
+        # module type or grouping) leaves the model untouched instead of half-pruned
+        cuts = [(m, probe.nan_indices[m]) for m in cascading_modules if probe.nan_indices.get(m) is not None]
+        for next_module, _ in cuts:
+            _check_prunable(next_module, "in")
+        _check_prunable(module, "out")
+        for next_module, idx in cuts:
+            self._prune_module(next_module, _as_index_array(idx), direction="in",
+                               original_len=probe.activation_len.get(next_module))
         self._prune_module(module, indices, direction="out")
 
     def prune_module(self, module, indices, direction="out", original_len=None):
@@ -97,21 +103,16 @@ class Pruner:
             return self._prune_module(module, self._sync(_as_index_array(indices)), direction, original_len)
 
     def _prune_module(self, module, indices, direction="out", original_len=None):
-        assert direction in ["out", "in"], "direction should be 'out' or 'in'"
-        if direction == "out":
-            assert any(isinstance(module, t) for t in SUPPORTED_OUT_PRUNING_MODULES), \
-                f"Cannot prune outgoing activations on this module. Only the following are supported " \
-                f"{SUPPORTED_OUT_PRUNING_MODULES}"
-        else:
-            assert any(isinstance(module, t) for t in SUPPORTED_IN_PRUNING_MODULES), \
-                f"Cannot prune incoming activations on this module. Only the following are supported " \
-                f"{SUPPORTED_IN_PRUNING_MODULES}"
-        if isinstance(module, _ConvNd) and module.groups != 1:
-            raise NotImplementedError("structured pruning of grouped convolutions is not supported")
+        _check_prunable(module, direction)
         indices = _as_index_array(indices)
         logger.info("Pruning %d units from %s (%s)", len(indices), module, direction)
         transposed = isinstance(module, _ConvTransposeNd)
-        if direction == "out":
+        if _is_depthwise(module):
+            # a per-channel pass-through: channel c is one (1, k, k) filter and one bias entry; the
+            # module stays depthwise at the new width
+            self.prune_parameters(module, ["weight", "bias"], indices, axis=0)
+            module.in_channels = module.out_channels = module.groups = module.weight.shape[0]
+        elif direction == "out":
             self.prune_parameter(module, "weight", indices, axis=1 if transposed else 0)
             self.prune_parameter(module, "bias", indices, axis=0)
             _set_width(module, "out", module.weight.shape[1 if transposed else 0])
@@ -273,6 +274,35 @@ class _ProbeRun:
     def __init__(self):
         self.nan_indices = {}
         self.activation_len = {}
+
+
+def _is_depthwise(module) -> bool:
+    """A grouped convolution with depth multiplier 1 (groups == in_channels == out_channels, one
+    input channel per filter), not transposed: a per-channel pass-through for structured pruning."""
+    return (isinstance(module, _ConvNd) and not isinstance(module, _ConvTransposeNd) and module.groups != 1
+            and module.groups == module.in_channels == module.out_channels and module.weight.shape[1] == 1)
+
+
+def _check_prunable(module, direction):
+    """Raise unless ``module`` can be cut along ``direction`` (called for every module of a
+    cascade before anything is sliced)."""
+    assert direction in ["out", "in"], "direction should be 'out' or 'in'"
+    if direction == "out":
+        assert any(isinstance(module, t) for t in SUPPORTED_OUT_PRUNING_MODULES), \
+            f"Cannot prune outgoing activations on this module. Only the following are supported " \
+            f"{SUPPORTED_OUT_PRUNING_MODULES}"
+    else:
+        assert any(isinstance(module, t) for t in SUPPORTED_IN_PRUNING_MODULES), \
+            f"Cannot prune incoming activations on this module. Only the following are supported " \
+            f"{SUPPORTED_IN_PRUNING_MODULES}"
+    if isinstance(module, _ConvNd) and module.groups != 1:
+        if not _is_depthwise(module):
+            raise NotImplementedError("structured pruning of grouped convolutions is not supported "
+                                      "(only depthwise convolutions with depth multiplier 1, as cascading modules)")
+        if direction == "out":
+            raise NotImplementedError("a depthwise convolution's outputs are tied one-to-one to its inputs: prune "
+                                      "the layer that produces its input and list the depthwise convolution among "
+                                      "that layer's cascading modules")
 
 
 def _set_width(module, direction, n):

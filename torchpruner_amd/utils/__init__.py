@@ -2,6 +2,7 @@ from .graph import (
     ACTIVATIONS,
     discover_cascade,
     find_best_module_for_attributions,
+    get_mobilenet_pruning_graph,
     get_resnet_pruning_graph,
     get_vgg_pruning_graph,
 )
@@ -12,6 +13,7 @@ __all__ = [
     "ACTIVATIONS",
     "discover_cascade",
     "find_best_module_for_attributions",
+    "get_mobilenet_pruning_graph",
     "get_resnet_pruning_graph",
     "get_vgg_pruning_graph",
     "count_parameters",

@@ -6,6 +6,8 @@
 * :func:`get_vgg_pruning_graph` — parity with graph.py:37-61 for chain CNNs.
 * :func:`get_resnet_pruning_graph` — new: residual-aware graph for bottleneck/basic-block
   ResNets (prune the block-internal convs, leave residual-tied convs alone).
+* :func:`get_mobilenet_pruning_graph` — new: the hidden channels of inverted-residual blocks
+  (expand conv -> BN -> depthwise conv -> BN -> project conv).
 * :func:`discover_cascade` — new: NaN-probe based consumer discovery for arbitrary graphs
   (SURVEY.md §7.3 hard part 6).
 """
@@ -94,6 +96,34 @@ def get_resnet_pruning_graph(model: nn.Module):
             cascade = [nxt] + ([bn] if isinstance(bn, _BatchNorm) else [])
             cascade.reverse()  # BN first, then the consumer conv (matches get_vgg_pruning_graph)
             graph.append((conv, cascade))
+    return graph[::-1]
+
+
+def get_mobilenet_pruning_graph(model: nn.Module):
+    """Pruning graph for MobileNetV2-style nets (inverted-residual blocks with a ``.conv``
+    Sequential of expand 1x1 conv, BN, activation, depthwise conv, BN, activation, project 1x1
+    conv, BN).
+
+    The expanded (hidden) channels of a block are private to it: cutting hidden channel c of the
+    expand conv cascades into its BN, the depthwise conv (a per-channel pass-through: one k x k
+    filter), the depthwise BN and one input column of the project conv. Blocks without expansion,
+    the stem, the project convs and the head write to the residual / inter-block stream and stay
+    intact, as in :func:`get_resnet_pruning_graph`. Returned last-block-first.
+    """
+    graph = []
+    for block in model.modules():
+        seq = getattr(block, "conv", None)
+        if not isinstance(seq, nn.Sequential):
+            continue
+        layers = [m for m in seq.modules() if isinstance(m, (nn.Conv2d, _BatchNorm))]
+        if len(layers) != 6 or not all(isinstance(layers[i], nn.Conv2d) for i in (0, 2, 4)) \
+                or not all(isinstance(layers[i], _BatchNorm) for i in (1, 3, 5)):
+            continue
+        expand, bn_expand, dw, bn_dw, project = layers[:5]
+        if expand.groups != 1 or project.groups != 1 or dw.groups == 1 \
+                or not (dw.groups == dw.in_channels == dw.out_channels == expand.out_channels):
+            continue
+        graph.append((expand, [bn_expand, dw, bn_dw, project]))
     return graph[::-1]
 
 
