@@ -328,7 +328,9 @@ at::Tensor maxpool_train_bwd(const at::Tensor& g_, const at::Tensor& am, int64_t
 }
 
 // Depthwise convolution (depth multiplier 1) on NHWC: x (B, H, W, C), w the (C, 1, k, k) parameter
-// read in place, k in {3, 5}, stride in {1, 2}, zero padding 0..k-1, any C.
+// read in place, k in {3, 5}, stride in {1, 2}, zero padding 0..k-1, any C. The activations may carry
+// more channels than the parameter (a pruned width at the kernels' granule): Cp = x.size(3) >
+// Cw = w.size(0) needs Cp % 4 == 0; the outputs' channels past Cw are exact zeros.
 void check_dw_geometry(int64_t H, int64_t W, int64_t k, int64_t s, int64_t pad) {
   TORCH_CHECK((k == 3 || k == 5) && (s == 1 || s == 2) && pad >= 0 && pad <= k - 1 && H + 2 * pad >= k &&
                   W + 2 * pad >= k, "bad depthwise conv geometry: k ", k, " stride ", s, " pad ", pad, " on ", H, "x", W);
@@ -336,8 +338,10 @@ void check_dw_geometry(int64_t H, int64_t W, int64_t k, int64_t s, int64_t pad) 
 
 void check_dw_weight(const at::Tensor& w, int64_t C, const at::Tensor& like) {
   check_cuda_f32(w, "w");
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == w.size(3) && w.is_contiguous() &&
-                  w.device() == like.device(), "w must be a contiguous (C, 1, k, k) depthwise weight");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) >= 1 && w.size(0) <= C && w.size(1) == 1 && w.size(2) == w.size(3) &&
+                  w.is_contiguous() && w.device() == like.device(),
+              "w must be a contiguous (Cw, 1, k, k) depthwise weight with Cw <= the activation's channels");
+  TORCH_CHECK(w.size(0) == C || C % 4 == 0, "a carried width (more channels than the weight) must be a multiple of 4");
 }
 
 at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t s,
@@ -352,14 +356,14 @@ at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
   const float* bp = nullptr;
   if (bias.has_value() && bias->defined()) {
     check_cuda_f32(*bias, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == C && bias->is_contiguous() && bias->device() == x.device(),
-                "bias must be a contiguous (C,) tensor");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == w.size(0) && bias->is_contiguous() &&
+                    bias->device() == x.device(), "bias must be a contiguous (Cw,) tensor");
     bp = bias->data_ptr<float>();
   }
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty({B, (H + 2 * pad - k) / s + 1, (W + 2 * pad - k) / s + 1, C}, x.options());
-  TP_CHECK_HIP(tp_dwconv_fwd(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)B, (int)H,
-                             (int)W, (int)C, (int)k, (int)s, (int)pad, cur_stream()));
+  TP_CHECK_HIP(tp_dwconv_fwd_cw(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)B, (int)H,
+                                (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
   return y;
 }
 
@@ -376,13 +380,14 @@ at::Tensor dwconv_dgrad(const at::Tensor& g_, const at::Tensor& w, int64_t H, in
               "dx exceeds the kernels' 2 GiB operand range");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   auto dx = at::empty({B, H, W, C}, g.options());
-  TP_CHECK_HIP(tp_dwconv_dgrad(g.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H,
-                               (int)W, (int)C, (int)k, (int)s, (int)pad, cur_stream()));
+  TP_CHECK_HIP(tp_dwconv_dgrad_cw(g.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H,
+                                  (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
   return dx;
 }
 
 // dW is written into ``dw`` with that tensor's own strides (the parameter's: DDP bucket views);
-// returns the bias gradient (C,) when asked for.
+// returns the bias gradient when asked for. dw's channel count Cw may be smaller than g / x's (a
+// carried width, a multiple of 4 then): the gradients cover the Cw channels of the parameter.
 c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x, int64_t k, int64_t s, int64_t pad,
                                        at::Tensor& dw, bool want_bias) {
   check_cuda_f32(g_, "g");
@@ -395,20 +400,23 @@ c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x
   check_dw_geometry(H, W, k, s, pad);
   const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
   TORCH_CHECK(g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo && g.size(3) == C, "g shape mismatch");
-  TORCH_CHECK(dw.dim() == 4 && dw.size(0) == C && dw.size(1) == 1 && dw.size(2) == k && dw.size(3) == k &&
-                  dw.device() == g.device() && dw.stride(0) > 0 && dw.stride(2) > 0 && dw.stride(3) > 0,
-              "dw must be a (C, 1, k, k) tensor with positive strides");
+  TORCH_CHECK(dw.dim() == 4 && dw.size(0) >= 1 && dw.size(0) <= C && dw.size(1) == 1 && dw.size(2) == k &&
+                  dw.size(3) == k && dw.device() == g.device() && dw.stride(0) > 0 && dw.stride(2) > 0 &&
+                  dw.stride(3) > 0,
+              "dw must be a (Cw, 1, k, k) tensor with positive strides, Cw <= the activations' channels");
+  const int64_t Cw = dw.size(0);
+  TORCH_CHECK(Cw == C || C % 4 == 0, "a carried width (more channels than dw) must be a multiple of 4");
   TORCH_CHECK(x.numel() < (int64_t(1) << 29) && g.numel() < (int64_t(1) << 29),
               "g / x exceed the kernels' 2 GiB operand range");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   const int chunks = tp_dwconv_wgrad_chunks((int)(B * Ho * Wo), (int)C);
   auto ws = at::empty({(int64_t)chunks * (k * k + 1) * C}, g.options().dtype(at::kDouble));
   c10::optional<at::Tensor> db;
-  if (want_bias) db = at::empty({C}, g.options());
-  TP_CHECK_HIP(tp_dwconv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
-                               want_bias ? db->data_ptr<float>() : nullptr, ws.data_ptr<double>(), chunks, (int)B,
-                               (int)H, (int)W, (int)C, (int)k, (int)s, (int)pad, dw.stride(0), dw.stride(2),
-                               dw.stride(3), cur_stream()));
+  if (want_bias) db = at::empty({Cw}, g.options());
+  TP_CHECK_HIP(tp_dwconv_wgrad_cw(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
+                                  want_bias ? db->data_ptr<float>() : nullptr, ws.data_ptr<double>(), chunks, (int)B,
+                                  (int)H, (int)W, (int)C, (int)Cw, (int)k, (int)s, (int)pad, dw.stride(0),
+                                  dw.stride(2), dw.stride(3), cur_stream()));
   return db;
 }
 

@@ -1068,6 +1068,9 @@ void wino_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t cfg, int64_t s
 // With ``relu`` also returns the ReLU bit mask (ceil(P*C/4) bytes; else an empty tensor) for bn_train_bwd.
 // Any C (C % 4 == 0: float4 rows; else per-element). ``cr`` (0 = C): the channels with parameters /
 // running statistics; x's channels c >= cr are the zero padding of a pruned width (outputs 0).
+// ``act``: the activation code, 0 none, 1 ReLU, 2 ReLU6 (y = min(max(v, 0), 6)); it wins over ``relu``
+// when non-zero, ``relu`` alone means 1. With an activation the bit mask is always returned (bit =
+// the gradient passes: v > 0, or 0 < v < 6 for ReLU6, whose backward has no other masking mode).
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
                                                              const c10::optional<at::Tensor>& beta,
                                                              const c10::optional<at::Tensor>& running_mean,
@@ -1075,7 +1078,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
                                                              double momentum, const c10::optional<at::Tensor>& res,
                                                              bool relu, const c10::optional<at::Tensor>& pre,
                                                              const c10::optional<at::Tensor>& num_batches,
-                                                             int64_t cr) {
+                                                             int64_t cr, int64_t act_) {
+  TORCH_CHECK(act_ >= 0 && act_ <= 2, "act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got ", act_);
+  const int act = act_ != 0 ? (int)act_ : (relu ? 1 : 0);
   need(x, "x", -1);
   const int64_t C = x.size(-1), P = x.numel() / std::max<int64_t>(C, 1);
   TORCH_CHECK(C > 0 && P > 0, "bn_train_fwd needs a non-empty batch");
@@ -1106,7 +1111,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
     nbt = reinterpret_cast<long long*>(num_batches->data_ptr<int64_t>());
   }
   auto y = at::empty_like(x);
-  auto mk = at::empty({relu ? (P * C + 3) / 4 : 0}, x.options().dtype(at::kByte));
+  auto mk = at::empty({act ? (P * C + 3) / 4 : 0}, x.options().dtype(at::kByte));
   const int64_t Cs = (C + 3) / 4 * 4;  // row stride: every row 16-byte aligned (float4 reads) for any C
   auto stats = at::empty({4, Cs}, x.options()).narrow(1, 0, C);  // mean, invstd, a, b
   float* sp = stats.data_ptr<float>();
@@ -1118,24 +1123,29 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
     auto ws = at::empty({2 * std::min<int64_t>(G, 256) * C}, x.options().dtype(at::kDouble));
     TP_CHECK_HIP(tp_bn_fwd_train_pre2(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
                                      (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(),
-                                     pre->data_ptr<double>(), (int)G, rp, relu ? 1 : 0,
-                                     relu ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
+                                     pre->data_ptr<double>(), (int)G, rp, act,
+                                     act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
     return {y, stats[0], stats[1], mk};
   }
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
   TP_CHECK_HIP(tp_bn_fwd_train5(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
                                 (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(), rp,
-                                relu ? 1 : 0, relu ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
+                                act, act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
   return {y, stats[0], stats[1], mk};
 }
 
 // Backward of bn_train_fwd: (dx or undefined, dgamma, dbeta, dres or undefined). ``ym``: the
 // forward output y when it was ReLU'd (the gradient is masked by y > 0 first); ``want_dres``:
-// also return that masked gradient (the residual branch's gradient).
+// also return that masked gradient (the residual branch's gradient). ``act``: the forward's
+// activation code; a ReLU6 forward (2) is masked by its bit mask only ("y > 0" is wrong for it).
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
     const at::Tensor& g, const at::Tensor& x, const c10::optional<at::Tensor>& gamma, const at::Tensor& mean,
     const at::Tensor& invstd, bool want_dx, const c10::optional<at::Tensor>& ym, bool want_dres,
-    const c10::optional<at::Tensor>& mask, int64_t cr, const c10::optional<at::Tensor>& pre) {
+    const c10::optional<at::Tensor>& mask, int64_t cr, const c10::optional<at::Tensor>& pre, int64_t act) {
+  TORCH_CHECK(act >= 0 && act <= 2, "act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got ", act);
+  TORCH_CHECK(act != 2 || ((!ym.has_value() || !ym->defined()) && mask.has_value() && mask->defined() &&
+                           mask->numel() > 0),
+              "the backward of a ReLU6 forward takes bn_train_fwd's bit mask, not ym");
   need(g, "g", -1);
   need(x, "x", -1);
   TORCH_CHECK(g.sizes() == x.sizes(), "g and x must have the same shape");
@@ -1205,9 +1215,10 @@ void register_engine_ops_def(torch::Library& m) {
   m.def("conv_gen_k(int ks, int Cin) -> int", &conv_gen_k);
   m.def("bn_train_fwd(Tensor x, Tensor? gamma, Tensor? beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
         "float eps, float momentum, Tensor? res=None, bool relu=False, Tensor? pre=None, "
-        "Tensor(c!)? num_batches=None, int cr=0) -> (Tensor, Tensor, Tensor, Tensor)");
+        "Tensor(c!)? num_batches=None, int cr=0, int act=0) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bn_train_bwd(Tensor g, Tensor x, Tensor? gamma, Tensor mean, Tensor invstd, bool want_dx, Tensor? ym=None, "
-        "bool want_dres=False, Tensor? mask=None, int cr=0, Tensor? pre=None) -> (Tensor, Tensor, Tensor, Tensor)");
+        "bool want_dres=False, Tensor? mask=None, int cr=0, Tensor? pre=None, int act=0) "
+        "-> (Tensor, Tensor, Tensor, Tensor)");
   m.def("conv_wgrad(Tensor g, Tensor x, int ks, int stride, int pad, int cfg, int splits, Tensor(a!)? out=None) "
         "-> Tensor");
   m.def("pack_conv_weight(Tensor w, int rows, int cols, int cpad, int mode) -> Tensor");

@@ -41,6 +41,14 @@ int tp_dwconv_wgrad_chunks(int P, int C);
 hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks, int B, int H,
                            int W, int C, int k, int s, int pad, long long s0, long long s2, long long s3,
                            hipStream_t st);
+// carried widths: activations of C channels per pixel, a parameter of Cw <= C (C % 4 == 0 when Cw < C)
+hipError_t tp_dwconv_fwd_cw(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C,
+                            int Cw, int k, int s, int pad, hipStream_t st);
+hipError_t tp_dwconv_dgrad_cw(const float* g, const float* w, float* dx, int B, int H, int W, int C, int Cw, int k,
+                              int s, int pad, hipStream_t st);
+hipError_t tp_dwconv_wgrad_cw(const float* g, const float* x, float* dw, float* db, double* ws, int chunks, int B,
+                              int H, int W, int C, int Cw, int k, int s, int pad, long long s0, long long s2,
+                              long long s3, hipStream_t st);
 // data_ops.hip
 hipError_t tp_augment_u8(const uint8_t* src, const int64_t* idx, const int* aug, int B, int C, int H, int W, int pad,
                          const float* mean, const float* inv_std, float* out, hipStream_t st);

@@ -38,6 +38,23 @@ __device__ __forceinline__ float4 relu_mask4(float4 d, const float* ym, size_t o
   return make_float4(m.x > 0.f ? d.x : 0.f, m.y > 0.f ? d.y : 0.f, m.z > 0.f ? d.z : 0.f, m.w > 0.f ? d.w : 0.f);
 }
 
+// The apply pass's activation code (the launchers' ``relu`` argument): 0 none, 1 ReLU, 2 ReLU6
+// (y = min(max(v, 0), 6); NaN propagates as in nan_relu). The mask bit means "the gradient passes":
+// v > 0 for ReLU, 0 < v < 6 (strict on both sides, ATen's hardtanh_backward) for ReLU6, read off the
+// clamped output (a value clamped to 6 fails "< 6", NaN fails both comparisons). A padding channel
+// (a = b = 0) gives v = 0: output 0, bit 0, for either activation.
+constexpr int BN_ACT_RELU6 = 2;
+__device__ __forceinline__ float bn_act(float v, int act) {
+  v = nan_relu(v);
+  return (act == BN_ACT_RELU6 && v > 6.f) ? 6.f : v;
+}
+__device__ __forceinline__ bool bn_act_bit(float y, int act) { return y > 0.f && (act != BN_ACT_RELU6 || y < 6.f); }
+// relu in 0..2, and ReLU6 only with a mask to write: the backward's other masking mode ("y > 0",
+// ym) is wrong for it
+static bool bn_act_ok(int relu, const uint8_t* mko) {
+  return relu >= 0 && relu <= BN_ACT_RELU6 && (relu != BN_ACT_RELU6 || mko != nullptr);
+}
+
 // 4 channels c..c+3 of row r: one float4 (V4) or per-element loads guarded by c + q < C
 template <bool V4>
 __device__ __forceinline__ float4 ld4(const float* __restrict__ t, size_t row_off, int c, int C) {
@@ -297,8 +314,8 @@ __global__ __launch_bounds__(256) void bn_apply_any(const float* __restrict__ x,
         float o = v * a[c] + b[c];
         if (res) o += res[e];
         if (relu) {
-          o = nan_relu(o);
-          bits |= o > 0.f ? (1u << q) : 0u;
+          o = bn_act(o, relu);
+          bits |= bn_act_bit(o, relu) ? (1u << q) : 0u;
         }
         out[e] = o;
       }
@@ -342,13 +359,13 @@ __global__ __launch_bounds__(256) void bn_apply(const float* __restrict__ x, con
         o.w += rv.w;
       }
       if (relu) {
-        o.x = nan_relu(o.x);
-        o.y = nan_relu(o.y);
-        o.z = nan_relu(o.z);
-        o.w = nan_relu(o.w);
-        if (mk)  // the backward's ReLU mask: bit q = output channel c+q is > 0
-          mk[t] = (uint8_t)((o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) |
-                            (o.w > 0.f ? 8u : 0u));
+        o.x = bn_act(o.x, relu);
+        o.y = bn_act(o.y, relu);
+        o.z = bn_act(o.z, relu);
+        o.w = bn_act(o.w, relu);
+        if (mk)  // the backward's mask: bit q = the gradient passes at output channel c+q
+          mk[t] = (uint8_t)((bn_act_bit(o.x, relu) ? 1u : 0u) | (bn_act_bit(o.y, relu) ? 2u : 0u) |
+                            (bn_act_bit(o.z, relu) ? 4u : 0u) | (bn_act_bit(o.w, relu) ? 8u : 0u));
       }
     }
     reinterpret_cast<float4*>(out)[t] = o;
@@ -415,15 +432,18 @@ static void partial_launch(dim3 grid, const float* x, const float* g, const floa
 }
 }  // namespace tp
 
-// Fused block tail: y = relu?(BN(x) + res?) (res: the residual branch, same shape as x). Any C;
-// channels c >= Cr are zero padding (no parameters, outputs 0).
-// mko (nullable, relu only): the ReLU bit mask, ceil(P*C/4) bytes (byte i, bit q = flat element 4i+q > 0)
+// Fused block tail: y = act(BN(x) + res?) (res: the residual branch, same shape as x). Any C;
+// channels c >= Cr are zero padding (no parameters, outputs 0). relu: the activation code, 0 none,
+// 1 ReLU, 2 ReLU6 (needs mko); anything else is rejected.
+// mko (nullable for ReLU, with an activation only): the bit mask, ceil(P*C/4) bytes (byte i, bit q =
+// the gradient passes at flat element 4i+q: > 0 for ReLU, strictly inside (0, 6) for ReLU6)
 extern "C" hipError_t tp_bn_fwd_train5(const float* x, float* y, int P, int C, int Cr, const float* gamma,
                                        const float* beta, float eps, float momentum, float* run_mean, float* run_var,
                                        float* mean, float* invstd, float* a, float* b, double* ws, const float* res,
                                        int relu, uint8_t* mko, long long* nbt, hipStream_t st) {
   using namespace tp;
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
+  if (!bn_act_ok(relu, mko)) return hipErrorInvalidValue;
   const int groups = bn_groups(P, C);
   const int rpg = (P + groups - 1) / groups;
   const dim3 grid((C + BN_CQ * 4 - 1) / (BN_CQ * 4), groups);
@@ -452,6 +472,7 @@ extern "C" hipError_t tp_bn_fwd_train_pre2(const float* x, float* y, int P, int 
                                            uint8_t* mko, long long* nbt, hipStream_t st) {
   using namespace tp;
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || G <= 0 || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
+  if (!bn_act_ok(relu, mko)) return hipErrorInvalidValue;
   const int G2 = std::min(G, 256), per = (G + G2 - 1) / G2;
   const int groups = (G + per - 1) / per;
   bn_fold_tiles<<<dim3((C + 63) / 64, groups), 256, 0, st>>>(pre, G, C, ws, per);

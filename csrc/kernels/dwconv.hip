@@ -18,6 +18,13 @@
 // [chunk][k*k + 1][C] (the last row is the bias gradient); a second kernel folds the chunks in a
 // fixed order and writes dW with the parameter's own strides. No atomics anywhere: every result
 // is deterministic.
+//
+// Carried widths (CARRY): the activations of a pruned block flow at a padded width C (a multiple of
+// 4) while the parameter has Cw < C channels. The float4 kernels then read x / g / y / dx at pitch
+// C; a quad wholly past Cw loads nothing and stores exact zeros, the quad that straddles Cw loads
+// its weights and bias per channel (guarded, zeros past Cw: a float4 load would run past the end of
+// the parameter) and stores exact zeros in its padding lanes whatever the inputs hold there; the
+// weight gradient reduces and writes the channels below Cw only.
 #include "tp_common.h"
 
 namespace tp {
@@ -58,12 +65,30 @@ __device__ __forceinline__ void dw_load_w(const float* __restrict__ w, int c, fl
   }
 }
 
+// dw_load_w for the quad that straddles Cw: per-channel loads, zero weights for c + v >= Cw
+template <int KK>
+__device__ __forceinline__ void dw_load_w_edge(const float* __restrict__ w, int c, int Cw, float* wf) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int i = 0; i < KK; ++i) wf[v * KK + i] = c + v < Cw ? w[(c + v) * KK + i] : 0.f;
+}
+
+// exact zeros for a strip's quad (the padding quads of a carried width)
+__device__ __forceinline__ void dw_store_zeros(float* p, int col0, int cols, int C) {
+  const float z[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < DW_SW; ++j)
+    if (col0 + j < cols) DwVec<4>::store(p + (col0 + j) * C, z);
+}
+
 // y[b, oh, ow, c] = bias[c] + sum_{kh, kw} x[b, oh*S - pad + kh, ow*S - pad + kw, c] * w[c, kh, kw]
-template <int K, int S, int V>
+template <int K, int S, int V, bool CARRY = false>
 __global__ __launch_bounds__(256) void dwconv_fwd_k(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ bias, float* __restrict__ y, int H,
                                                     int W, int C, int pad, int Ho, int Wo, int cpr, FastDiv dcv,
-                                                    int nq) {
+                                                    int nq, int Cw = 0) {
+  static_assert(!CARRY || V == 4, "carried widths run on the float4 path");
   constexpr int KK = K * K, NIN = (DW_SW - 1) * S + K;
   const int row = blockIdx.x / cpr, chunk = blockIdx.x - row * cpr;  // row = b * Ho + oh
   const int q = chunk * 256 + threadIdx.x;
@@ -71,14 +96,35 @@ __global__ __launch_bounds__(256) void dwconv_fwd_k(const float* __restrict__ x,
   const int strip = dcv.div(q), c = (q - strip * (C / V)) * V;
   const int b = row / Ho, oh = row - b * Ho;
   const int ow0 = strip * DW_SW, ih0 = oh * S - pad, iw0 = ow0 * S - pad;
+  float* yr = y + row * Wo * C + c;
+  bool edge = false;  // the quad straddles Cw
+  if constexpr (CARRY) {
+    if (c >= Cw) {
+      dw_store_zeros(yr, ow0, Wo, C);
+      return;
+    }
+    edge = c + 4 > Cw;
+  }
   float wf[V * KK];
-  dw_load_w<V, KK>(w, c, wf);
+  if constexpr (CARRY) {
+    if (edge) dw_load_w_edge<KK>(w, c, Cw, wf);
+    else dw_load_w<V, KK>(w, c, wf);
+  } else {
+    dw_load_w<V, KK>(w, c, wf);
+  }
   float acc[DW_SW][V];
   {
     float bv[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) bv[v] = 0.f;
-    if (bias != nullptr) DwVec<V>::load(bias + c, bv);
+    if (bias != nullptr) {
+      if (edge) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) bv[v] = c + v < Cw ? bias[c + v] : 0.f;
+      } else {
+        DwVec<V>::load(bias + c, bv);
+      }
+    }
 #pragma unroll
     for (int j = 0; j < DW_SW; ++j)
 #pragma unroll
@@ -104,7 +150,14 @@ __global__ __launch_bounds__(256) void dwconv_fwd_k(const float* __restrict__ x,
 #pragma unroll
         for (int v = 0; v < V; ++v) acc[j][v] = fmaf(in[j * S + kw][v], wf[v * KK + kh * K + kw], acc[j][v]);
   }
-  float* yr = y + row * Wo * C + c;
+  if constexpr (CARRY) {
+    if (edge) {  // exact zeros in the padding lanes, whatever x holds there (0 * inf would be NaN)
+#pragma unroll
+      for (int j = 0; j < DW_SW; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[j][v] = c + v < Cw ? acc[j][v] : 0.f;
+    }
+  }
 #pragma unroll
   for (int j = 0; j < DW_SW; ++j)
     if (ow0 + j < Wo) DwVec<V>::store(yr + (ow0 + j) * C, acc[j]);
@@ -134,10 +187,11 @@ struct DwTaps {
   }
 };
 
-template <int K, int S, int PB, int V>
+template <int K, int S, int PB, int V, bool CARRY = false>
 __global__ __launch_bounds__(256) void dwconv_dgrad_k(const float* __restrict__ g, const float* __restrict__ w,
                                                       float* __restrict__ dx, int H, int W, int C, int pad, int Ho,
-                                                      int Wo, int cpr, FastDiv dcv, int nq) {
+                                                      int Wo, int cpr, FastDiv dcv, int nq, int Cw = 0) {
+  static_assert(!CARRY || V == 4, "carried widths run on the float4 path");
   constexpr int KK = K * K, DMIN = DwTaps<K, S, PB>::lo(), ND = DwTaps<K, S, PB>::hi() - DMIN + 1;
   const int row = blockIdx.x / cpr, chunk = blockIdx.x - row * cpr;  // row = b * H + ih
   const int q = chunk * 256 + threadIdx.x;
@@ -146,8 +200,22 @@ __global__ __launch_bounds__(256) void dwconv_dgrad_k(const float* __restrict__ 
   const int b = row / H, ih = row - b * H;
   const int iw0 = strip * DW_SW;
   const int ow_lo = (iw0 + pad - PB) / S + DMIN;  // exact division: (iw0 + pad) % S == PB
+  float* dr = dx + row * W * C + c;
+  bool edge = false;  // the quad straddles Cw
+  if constexpr (CARRY) {
+    if (c >= Cw) {
+      dw_store_zeros(dr, iw0, W, C);
+      return;
+    }
+    edge = c + 4 > Cw;
+  }
   float wf[V * KK];
-  dw_load_w<V, KK>(w, c, wf);
+  if constexpr (CARRY) {
+    if (edge) dw_load_w_edge<KK>(w, c, Cw, wf);
+    else dw_load_w<V, KK>(w, c, wf);
+  } else {
+    dw_load_w<V, KK>(w, c, wf);
+  }
   float acc[DW_SW][V];
 #pragma unroll
   for (int j = 0; j < DW_SW; ++j)
@@ -178,7 +246,14 @@ __global__ __launch_bounds__(256) void dwconv_dgrad_k(const float* __restrict__ 
             acc[j][v] = fmaf(gv[(PB + j - kw) / S - DMIN][v], wf[v * KK + kh * K + kw], acc[j][v]);
         }
   }
-  float* dr = dx + row * W * C + c;
+  if constexpr (CARRY) {
+    if (edge) {  // exact zeros in the padding lanes, whatever g holds there
+#pragma unroll
+      for (int j = 0; j < DW_SW; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[j][v] = c + v < Cw ? acc[j][v] : 0.f;
+    }
+  }
 #pragma unroll
   for (int j = 0; j < DW_SW; ++j)
     if (iw0 + j < W) DwVec<V>::store(dr + (iw0 + j) * C, acc[j]);
@@ -194,12 +269,16 @@ template <int K, int S, int V>
 __global__ __launch_bounds__(256) void dwconv_wgrad_k(const float* __restrict__ g, const float* __restrict__ x,
                                                       double* __restrict__ ws, int H, int W, int C, int pad, int Ho,
                                                       int Wo, int U, int upc, int nstr, int cxs, FastDiv dstr,
-                                                      FastDiv dho) {
+                                                      FastDiv dho, int Cw) {
   constexpr int KK = K * K, NT = KK + 1, NIN = (DW_SW - 1) * S + K;
   const int PT = 256 >> cxs;
   const int cx = threadIdx.x & ((1 << cxs) - 1), py = threadIdx.x >> cxs;
   const int c = ((blockIdx.x << cxs) + cx) * V;
-  const bool active = c < C;  // (C % V == 0: a channel vector is inside or outside as a whole)
+  // C % V == 0: a channel vector is inside or outside the pitch C as a whole. Cw <= C: the channels
+  // with parameters; a quad wholly past Cw does no work (its workspace rows stay unwritten and the
+  // fold never reads them), the padding lanes of the quad that straddles Cw are reduced like any
+  // other lane (whatever g / x hold there) and dropped by the fold
+  const bool active = c < Cw;
   const int chunk = blockIdx.y;
   const int u0 = chunk * upc, u1 = min(U, u0 + upc);
   float acc[NT][V];
@@ -274,21 +353,22 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_k(const float* __restrict__ 
 // is bound by load latency), then lane 0 adds the 16 partials in lane order; all in fp64.
 __global__ __launch_bounds__(256) void dwconv_wgrad_fold(const double* __restrict__ ws, float* __restrict__ dw,
                                                          float* __restrict__ db, int chunks, int C, int K,
-                                                         long long s0, long long s2, long long s3) {
+                                                         long long s0, long long s2, long long s3, int Cw) {
   const int KK = K * K, NT = KK + 1, n = NT * C;
   const int e = threadIdx.x & 15, l = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + e;
+  const int t = i / C, c = i - t * C;
+  const bool real = i < n && c < Cw;  // dW / db have Cw channels: the padding of a carried width is skipped
   double s = 0.0;
-  if (i < n)
+  if (real)
     for (int ch = l; ch < chunks; ch += 16) s += ws[ch * n + i];
   __shared__ double part[16][16];
   part[l][e] = s;
   __syncthreads();
-  if (l != 0 || i >= n) return;
+  if (l != 0 || !real) return;
   s = 0.0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) s += part[j][e];
-  const int t = i / C, c = i - t * C;
   if (t < KK) {
     const int kh = t / K, kw = t - kh * K;
     dw[c * s0 + kh * s2 + kw * s3] = (float)s;
@@ -348,47 +428,66 @@ static bool dw_row_grid(int rows, int cols, int C, int V, int* cpr, int* nq, lon
     else fn(5, 2, __VA_ARGS__);                \
   } while (0)
 
-// y = dwconv(x, w) (+ bias): x (B, H, W, C), w (C, 1, k, k), y (B, Ho, Wo, C)
-extern "C" hipError_t tp_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
-                                    int C, int k, int s, int pad, hipStream_t st) {
+// A carried width: the activations have C channels per pixel, the parameter Cw <= C of them; the
+// float4 path (C % 4 == 0) is the only one that takes Cw < C
+static bool dw_carried_ok(int C, int Cw) { return Cw > 0 && Cw <= C && (Cw == C || C % 4 == 0); }
+
+// y = dwconv(x, w) (+ bias): x (B, H, W, C), w (Cw, 1, k, k), bias (Cw), y (B, Ho, Wo, C); the channels
+// c >= Cw of y are exact zeros, whatever x holds there
+extern "C" hipError_t tp_dwconv_fwd_cw(const float* x, const float* w, const float* bias, float* y, int B, int H,
+                                       int W, int C, int Cw, int k, int s, int pad, hipStream_t st) {
   int Ho, Wo, cpr, nq;
   long long blocks;
-  if (!tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, x, w, bias, y))
+  if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, x, w, bias, y))
     return hipErrorInvalidValue;
   const int V = C % 4 == 0 ? 4 : 1;
   if (!tp::dw_row_grid(B * Ho, Wo, C, V, &cpr, &nq, &blocks)) return hipErrorInvalidValue;
   const tp::FastDiv dcv((unsigned)(C / V));
-#define TP_DW_FWD(K_, S_, V_) \
-  tp::dwconv_fwd_k<K_, S_, V_><<<(unsigned)blocks, 256, 0, st>>>(x, w, bias, y, H, W, C, pad, Ho, Wo, cpr, dcv, nq)
-  if (V == 4) TP_DW_KS(TP_DW_FWD, 4);
-  else TP_DW_KS(TP_DW_FWD, 1);
+#define TP_DW_FWD(K_, S_, V_, CARRY_)                                                                                \
+  tp::dwconv_fwd_k<K_, S_, V_, CARRY_><<<(unsigned)blocks, 256, 0, st>>>(x, w, bias, y, H, W, C, pad, Ho, Wo, cpr, dcv, \
+                                                                         nq, Cw)
+  if (Cw < C) TP_DW_KS(TP_DW_FWD, 4, true);
+  else if (V == 4) TP_DW_KS(TP_DW_FWD, 4, false);
+  else TP_DW_KS(TP_DW_FWD, 1, false);
 #undef TP_DW_FWD
   return hipGetLastError();
 }
 
-// dx (B, H, W, C) from g (B, Ho, Wo, C)
-extern "C" hipError_t tp_dwconv_dgrad(const float* g, const float* w, float* dx, int B, int H, int W, int C, int k,
-                                      int s, int pad, hipStream_t st) {
+extern "C" hipError_t tp_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
+                                    int C, int k, int s, int pad, hipStream_t st) {
+  return tp_dwconv_fwd_cw(x, w, bias, y, B, H, W, C, C, k, s, pad, st);
+}
+
+// dx (B, H, W, C) from g (B, Ho, Wo, C) and w (Cw, 1, k, k); the channels c >= Cw of dx are exact zeros
+extern "C" hipError_t tp_dwconv_dgrad_cw(const float* g, const float* w, float* dx, int B, int H, int W, int C, int Cw,
+                                         int k, int s, int pad, hipStream_t st) {
   int Ho, Wo, cpr, nq;
   long long blocks;
-  if (!tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, w, dx)) return hipErrorInvalidValue;
+  if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, w, dx))
+    return hipErrorInvalidValue;
   const int V = C % 4 == 0 ? 4 : 1;
   if (!tp::dw_row_grid(B * H, W, C, V, &cpr, &nq, &blocks)) return hipErrorInvalidValue;
   const tp::FastDiv dcv((unsigned)(C / V));
   const int pb = pad % s;  // parity of iw0 + pad (strips start at multiples of 4)
-#define TP_DW_DG(K_, S_, V_)                                                                                      \
-  do {                                                                                                            \
-    if (S_ == 2 && pb == 1)                                                                                       \
-      tp::dwconv_dgrad_k<K_, S_, S_ - 1, V_><<<(unsigned)blocks, 256, 0, st>>>(g, w, dx, H, W, C, pad, Ho, Wo, cpr, \
-                                                                               dcv, nq);                          \
-    else                                                                                                          \
-      tp::dwconv_dgrad_k<K_, S_, 0, V_><<<(unsigned)blocks, 256, 0, st>>>(g, w, dx, H, W, C, pad, Ho, Wo, cpr, dcv, \
-                                                                          nq);                                    \
+#define TP_DW_DG(K_, S_, V_, CARRY_)                                                                               \
+  do {                                                                                                             \
+    if (S_ == 2 && pb == 1)                                                                                        \
+      tp::dwconv_dgrad_k<K_, S_, S_ - 1, V_, CARRY_><<<(unsigned)blocks, 256, 0, st>>>(g, w, dx, H, W, C, pad, Ho, Wo, \
+                                                                                       cpr, dcv, nq, Cw);          \
+    else                                                                                                           \
+      tp::dwconv_dgrad_k<K_, S_, 0, V_, CARRY_><<<(unsigned)blocks, 256, 0, st>>>(g, w, dx, H, W, C, pad, Ho, Wo, cpr, \
+                                                                                  dcv, nq, Cw);                    \
   } while (0)
-  if (V == 4) TP_DW_KS(TP_DW_DG, 4);
-  else TP_DW_KS(TP_DW_DG, 1);
+  if (Cw < C) TP_DW_KS(TP_DW_DG, 4, true);
+  else if (V == 4) TP_DW_KS(TP_DW_DG, 4, false);
+  else TP_DW_KS(TP_DW_DG, 1, false);
 #undef TP_DW_DG
   return hipGetLastError();
+}
+
+extern "C" hipError_t tp_dwconv_dgrad(const float* g, const float* w, float* dx, int B, int H, int W, int C, int k,
+                                      int s, int pad, hipStream_t st) {
+  return tp_dwconv_dgrad_cw(g, w, dx, B, H, W, C, C, k, s, pad, st);
 }
 
 // Chunks of the wgrad grid for P = B * Ho * Wo output pixels: about eight blocks per CU over the
@@ -401,19 +500,22 @@ extern "C" int tp_dwconv_wgrad_chunks(int P, int C) {
   return std::min(chunks, std::max(1, P / 256));
 }
 
-// dW[c, 0, kh, kw] at dw[c * s0 + kh * s2 + kw * s3] (the parameter's own strides, in elements) and,
-// with db, db[c] = sum g; ws: tp_dwconv_wgrad_chunks(P, C) * (k*k + 1) * C doubles, chunks = that count
-extern "C" hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
-                                      int B, int H, int W, int C, int k, int s, int pad, long long s0, long long s2,
-                                      long long s3, hipStream_t st) {
+// dW[c, 0, kh, kw] at dw[c * s0 + kh * s2 + kw * s3] (the parameter's own strides, in elements) for
+// the Cw channels of the parameter and, with db, db[c] = sum g (Cw entries); g / x carry C >= Cw
+// channels per pixel. ws: tp_dwconv_wgrad_chunks(P, C) * (k*k + 1) * C doubles (sized by the carried
+// width), chunks = that count
+extern "C" hipError_t tp_dwconv_wgrad_cw(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
+                                         int B, int H, int W, int C, int Cw, int k, int s, int pad, long long s0,
+                                         long long s2, long long s3, hipStream_t st) {
   int Ho, Wo;
-  if (!tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, x, ws)) return hipErrorInvalidValue;
+  if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, x, ws))
+    return hipErrorInvalidValue;
   const int P = B * Ho * Wo;
   if (dw == nullptr || ws == nullptr || ((uintptr_t)ws & 7) || ((uintptr_t)dw & 3) || ((uintptr_t)db & 3))
     return hipErrorInvalidValue;
   if (chunks != tp_dwconv_wgrad_chunks(P, C) || s0 < 1 || s2 < 1 || s3 < 1) return hipErrorInvalidValue;
   if (s0 >= tp::DW_MAX_BYTES || s2 >= tp::DW_MAX_BYTES || s3 >= tp::DW_MAX_BYTES) return hipErrorInvalidValue;
-  if ((s0 * (C - 1) + s2 * (k - 1) + s3 * (k - 1) + 1) * 4 >= tp::DW_MAX_BYTES) return hipErrorInvalidValue;
+  if ((s0 * (Cw - 1) + s2 * (k - 1) + s3 * (k - 1) + 1) * 4 >= tp::DW_MAX_BYTES) return hipErrorInvalidValue;
   if (tp::ceil_div((long long)(k * k + 1) * C, 16) >= tp::DW_MAX_BLOCKS) return hipErrorInvalidValue;  // the fold's grid
   const int V = C % 4 == 0 ? 4 : 1, CV = C / V;
   int cxs = 0;  // 2^cxs channel vectors per block: up to 64 channels, no more than the layer has
@@ -422,12 +524,19 @@ extern "C" hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw,
   const int upc = (U + chunks - 1) / chunks;
   const dim3 grid((CV + (1 << cxs) - 1) >> cxs, chunks);
   const tp::FastDiv dstr((unsigned)nstr), dho((unsigned)Ho);
-#define TP_DW_WG(K_, S_, V_) \
-  tp::dwconv_wgrad_k<K_, S_, V_><<<grid, 256, 0, st>>>(g, x, ws, H, W, C, pad, Ho, Wo, U, upc, nstr, cxs, dstr, dho)
+#define TP_DW_WG(K_, S_, V_)                                                                                          \
+  tp::dwconv_wgrad_k<K_, S_, V_><<<grid, 256, 0, st>>>(g, x, ws, H, W, C, pad, Ho, Wo, U, upc, nstr, cxs, dstr, dho, \
+                                                       Cw)
   if (V == 4) TP_DW_KS(TP_DW_WG, 4);
   else TP_DW_KS(TP_DW_WG, 1);
 #undef TP_DW_WG
   const int n = (k * k + 1) * C;
-  tp::dwconv_wgrad_fold<<<tp::ceil_div(n, 16), 256, 0, st>>>(ws, dw, db, chunks, C, k, s0, s2, s3);
+  tp::dwconv_wgrad_fold<<<tp::ceil_div(n, 16), 256, 0, st>>>(ws, dw, db, chunks, C, k, s0, s2, s3, Cw);
   return hipGetLastError();
+}
+
+extern "C" hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
+                                      int B, int H, int W, int C, int k, int s, int pad, long long s0, long long s2,
+                                      long long s3, hipStream_t st) {
+  return tp_dwconv_wgrad_cw(g, x, dw, db, ws, chunks, B, H, W, C, C, k, s, pad, s0, s2, s3, st);
 }

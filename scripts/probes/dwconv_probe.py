@@ -8,10 +8,15 @@ JIT / solver search the library pays), then forward + backward (dgrad + wgrad) o
 both paths in alternating rounds timed with device events, and the three native kernels alone
 with their achieved bytes/s over the floor of one read and one write of the activation
 (forward: x + y, dgrad: g + dx, wgrad: g + x) against the 6.29 TB/s measured copy rate. The
-spread is what the native side's own rounds show. Last, one whole training step of a pruned
-MobileNetV2 both ways.
+spread is what the native side's own rounds show. Last, one whole training step of MobileNetV2,
+dense and pruned, three ways in alternating rounds: the default (fused BN + ReLU6 tails, carried
+hidden widths, the inverted-residual block forward), the same build with those fusions off
+(TORCHPRUNER_FUSE_RELU6=0's path) and with the depthwise convs on the library path; those lines also
+go to --step-out.
 
     python scripts/probes/dwconv_probe.py [--batch 128] [--out profiles/dwconv/dwconv_vs_library.txt]
+    python scripts/probes/dwconv_probe.py --step-only [--no-library] [--step-out profiles/dwconv/mobilenet_step_fused.txt]
+    python scripts/probes/dwconv_probe.py --trace-steps 3 --variant fused|unfused   (under rocprofv3 --kernel-trace)
 """
 import argparse
 import copy
@@ -102,33 +107,50 @@ def probe_shape(C, H, s, B, rounds, emit):
     return mn, ml, spread, first
 
 
-def probe_step(B, rounds, emit):
-    """One training step of MobileNetV2 (224 px) with every hidden width cut by 30 % + 1, dense
-    convs native on both sides, depthwise convs native vs library."""
+def step_model(B, pruned):
+    """MobileNetV2 (224 px), dense or with every hidden width cut by 30 % + 1, and one batch."""
     dev = torch.device("cuda")
     torch.manual_seed(0)
     model = mobilenet_v2(1000).to(dev)
-    rng = np.random.RandomState(0)
-    pruner = Pruner(model, (3, 224, 224), dev)
-    for module, cascade in get_mobilenet_pruning_graph(model):
-        n = module.weight.shape[0]
-        pruner.prune_model(module, rng.choice(n, int(n * 0.3) + 1, replace=False), cascade)
+    if pruned:
+        rng = np.random.RandomState(0)
+        pruner = Pruner(model, (3, 224, 224), dev)
+        for module, cascade in get_mobilenet_pruning_graph(model):
+            n = module.weight.shape[0]
+            pruner.prune_model(module, rng.choice(n, int(n * 0.3) + 1, replace=False), cascade)
     model = model.to(memory_format=torch.channels_last).train()
     x = torch.randn(B, 3, 224, 224, device=dev).contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 1000, (B,), device=dev)
-    steps = {}
-    for name, flag in (("native", True), ("library", False)):
-        m = copy.deepcopy(model)
-        train._NATIVE_DW = flag
-        train.enable_native_convs(m)
-        train._NATIVE_DW = True
-        opt = torch.optim.SGD(m.parameters(), lr=0.01, momentum=0.9, fused=True)
+    return model, x, y
 
-        def step(m=m, opt=opt):
-            opt.zero_grad(set_to_none=True)
-            F.cross_entropy(m(x), y).backward()
-            opt.step()
-        steps[name] = step
+
+# variant -> (_NATIVE_DW, _MB_FUSE) while enable_native_convs installs the forwards
+VARIANTS = {"fused": (True, True), "unfused": (True, False), "library": (False, True)}
+
+
+def make_step(model, x, y, variant):
+    m = copy.deepcopy(model)
+    keep = train._NATIVE_DW, train._MB_FUSE
+    train._NATIVE_DW, train._MB_FUSE = VARIANTS[variant]
+    train.enable_native_convs(m)
+    train._NATIVE_DW, train._MB_FUSE = keep
+    opt = torch.optim.SGD(m.parameters(), lr=0.01, momentum=0.9, fused=True)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        F.cross_entropy(m(x), y).backward()
+        opt.step()
+    return step
+
+
+def probe_step(B, rounds, emit, pruned=True, library=True):
+    """One training step of MobileNetV2 (224 px), dense or with every hidden width cut by 30 % + 1,
+    dense convs native on every side: the fused default, the fusions off (the path before them:
+    native BN then ATen hardtanh, hidden widths sliced, depthwise convs at their real width) and
+    the depthwise convs on the library path. Alternating rounds, device events; each side's spread
+    is (max - min) / median over its own rounds."""
+    model, x, y = step_model(B, pruned)
+    steps = {v: make_step(model, x, y, v) for v in VARIANTS if library or v != "library"}
     first = {n: first_call(f) for n, f in steps.items()}
     for f in steps.values():
         f()
@@ -136,10 +158,30 @@ def probe_step(B, rounds, emit):
     for _ in range(rounds):
         for n, f in steps.items():
             t[n].append(timed(f, 3))
-    mn, ml = float(np.median(t["native"])), float(np.median(t["library"]))
-    emit(f"pruned MobileNetV2 step B={B} 224px: depthwise native {mn:.2f} ms  library {ml:.2f} ms  lib/nat {ml / mn:.2f}x  "
-         f"spread {(max(t['native']) - min(t['native'])) / mn * 100:.1f}%  first step native {first['native'] / 1e3:.1f} s "
-         f"library {first['library'] / 1e3:.1f} s")
+    med = {n: float(np.median(v)) for n, v in t.items()}
+    spread = {n: (max(v) - min(v)) / med[n] * 100 for n, v in t.items()}
+    what = "pruned" if pruned else "dense"
+    line = (f"{what} MobileNetV2 step B={B} 224px, {rounds} alternating rounds of 3 steps: "
+            f"fused {med['fused']:.2f} ms (spread {spread['fused']:.1f}%)  "
+            f"unfused {med['unfused']:.2f} ms (spread {spread['unfused']:.1f}%)  "
+            f"unfused/fused {med['unfused'] / med['fused']:.3f}x")
+    if "library" in steps:
+        line += (f"  depthwise on the library path {med['library']:.2f} ms (spread {spread['library']:.1f}%)  "
+                 f"library/fused {med['library'] / med['fused']:.2f}x")
+    line += "  first step " + " ".join(f"{n} {first[n] / 1e3:.1f} s" for n in steps)
+    emit(line)
+    return med, spread
+
+
+def trace_steps(B, variant, n):
+    """A few pruned steps of one variant and nothing else: the program of a
+    ``rocprofv3 --kernel-trace --stats`` run (tuning and warm-up steps are part of the trace; the
+    per-kernel summary is taken over all of them)."""
+    model, x, y = step_model(B, True)
+    step = make_step(model, x, y, variant)
+    for _ in range(n):
+        step()
+    torch.cuda.synchronize()
 
 
 def main():
@@ -148,7 +190,37 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--budget", type=float, default=900.0, help="seconds after which remaining shapes are skipped")
     ap.add_argument("--out", default=os.path.join("profiles", "dwconv", "dwconv_vs_library.txt"))
+    ap.add_argument("--step-out", default=os.path.join("profiles", "dwconv", "mobilenet_step_fused.txt"))
+    ap.add_argument("--step-only", action="store_true", help="only the whole-step comparison")
+    ap.add_argument("--step-rounds", type=int, default=5)
+    ap.add_argument("--no-library", action="store_true", help="whole step: leave the library-path variant out")
+    ap.add_argument("--trace-steps", type=int, default=0, help="run this many pruned steps of --variant and exit")
+    ap.add_argument("--variant", choices=sorted(VARIANTS), default="fused")
     a = ap.parse_args()
+    if a.trace_steps:
+        trace_steps(a.batch, a.variant, a.trace_steps)
+        return
+    os.makedirs(os.path.dirname(a.step_out) or ".", exist_ok=True)
+    step_out = open(a.step_out, "w")
+
+    def emit_step(line):
+        print(line, flush=True)
+        for f in (step_out,) if a.step_only else (out, step_out):
+            f.write(line + "\n")
+            f.flush()
+
+    def steps():
+        emit_step(f"# dwconv_probe whole step: {torch.cuda.get_device_name(0)}, torch {torch.__version__}, fp32 "
+                  f"channels_last, SGD momentum (fused optimizer); fused = the default path, unfused = "
+                  f"TORCHPRUNER_FUSE_RELU6=0's path in the same process; median ms per step, device events")
+        for pruned in (False, True):
+            probe_step(a.batch, a.step_rounds, emit_step, pruned=pruned, library=not a.no_library)
+            torch.cuda.empty_cache()
+        step_out.close()
+
+    if a.step_only:
+        steps()
+        return
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     out = open(a.out, "w")
 
@@ -181,7 +253,7 @@ def main():
     emit("shapes where native loses by more than its spread: " +
          (", ".join(f"C={c} {h}x{h} s{s} ({r:.2f}x)" for c, h, s, r in loses) or "none"))
     if time.perf_counter() - t0 < a.budget:
-        probe_step(a.batch, 3, emit)
+        steps()
     else:
         emit("whole step: skipped (time budget)")
     out.close()

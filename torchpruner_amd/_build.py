@@ -252,6 +252,34 @@ def build_dwconv_sanitizer(verbose: bool = False) -> Path:
     return exe
 
 
+def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
+    """Build ``csrc/tests/dwconv_carried_validation.cpp`` against the carried-width depthwise-conv
+    launchers (``dwconv.hip``) and the BatchNorm launchers (``batchnorm.hip``) with
+    AddressSanitizer + UBSan on the HOST code only, like :func:`build_dwconv_sanitizer` (the two
+    kernel objects are the ones that build and :func:`build_host_sanitizer` make). Returns the
+    executable path."""
+    out_dir = ROOT / "build" / "asan"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    headers = sorted((CSRC / "include").glob("*.h"))
+    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    jobs, objs = [], []
+    for name in ("dwconv", "batchnorm"):
+        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
+        objs.append(obj)
+        if _needs_rebuild(src, obj, headers):
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
+                         "-c", src, "-o", obj])
+    test_src, test_obj = CSRC / "tests" / "dwconv_carried_validation.cpp", out_dir / "dwconv_carried_validation.o"
+    if _needs_rebuild(test_src, test_obj, headers):
+        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san, "-c", test_src, "-o", test_obj])
+    with ThreadPoolExecutor(max_workers=3) as ex:
+        list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / "dwconv_carried_validation"
+    if jobs or not exe.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
+    return exe
+
+
 if __name__ == "__main__":
     build(verbose=True, force="--force" in sys.argv)
     print(OUT)

@@ -18,6 +18,10 @@ Depthwise convolutions (depth multiplier 1, 3x3 / 5x5, stride 1 / 2, any width) 
 kernels (``tpamd.dwconv_fwd`` / ``dwconv_dgrad`` / ``dwconv_wgrad``): memory-bound, no MFMA, no
 tuner, the weights read from the parameter in place; every prune round of a MobileNet changes the
 width of every one of them, which on the library path is a new shape to compile each time.
+Inside an inverted-residual block (:func:`_native_ir_forward`) the hidden activation keeps its
+carried width from the expand conv through BN + ReLU6 (one fused apply pass, ``bn_act(act=2)``) and
+the depthwise conv (float4 kernels at any pruned width) into the project conv, whose BN takes the
+shortcut in its apply pass; ``TORCHPRUNER_FUSE_RELU6=0`` keeps the unfused path.
 
 Training-mode ``BatchNorm2d`` runs on deterministic NHWC batch-statistics / normalisation /
 backward kernels (K5, ``tpamd.bn_train_*``), training-mode ``nn.Dropout`` on a counter-based
@@ -161,9 +165,14 @@ _BATCH_PACK = os.environ.get("TORCHPRUNER_BATCH_WEIGHT_PACK", "1") != "0"
 # TORCHPRUNER_BN_BWD_FUSE=0: a bottleneck's backward keeps the separate BN statistics pass and the
 # materialised residual gradient (A/B switch, read once per process)
 _BWD_FUSE = os.environ.get("TORCHPRUNER_BN_BWD_FUSE", "1") != "0"
-# backward passes that took each fusion (tests / diagnostics): tail statistics from a dgrad epilogue,
-# identity gradients handed over unmasked
-FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0}
+# TORCHPRUNER_FUSE_RELU6=0: BN + ReLU6 tails stay unfused (the native BN, then ATen's hardtanh), ReLU6
+# takes the real-width slice of a carried activation and inverted-residual blocks keep their module
+# forward (A/B switch, read once; consulted when enable_native_convs installs forwards)
+_MB_FUSE = os.environ.get("TORCHPRUNER_FUSE_RELU6", "1") != "0"
+# passes that took each fusion (tests / diagnostics). Backward: tail statistics from a dgrad epilogue,
+# identity gradients handed over unmasked. Forward: fused BN + ReLU6 tails, inverted-residual blocks
+# on the fused block forward, depthwise convs on a carried (padded) width
+FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0, "bn_relu6": 0, "ir_block": 0, "dw_carried": 0}
 # TORCHPRUNER_NATIVE_DW=0: depthwise convs stay on the library path (A/B switch, read once)
 _NATIVE_DW = os.environ.get("TORCHPRUNER_NATIVE_DW", "1") != "0"
 # launches of the depthwise kernels (tests / diagnostics)
@@ -675,25 +684,29 @@ def _nhwc(t: torch.Tensor) -> torch.Tensor:
 
 
 class _NativeBNAct(torch.autograd.Function):
-    """Fused training-mode block tail ``relu?(BN(x) + res?)`` (BN statistics, normalisation,
-    residual add and ReLU in one apply pass). The backward masks the gradient by the saved output
-    (ReLU), returns it as the residual branch's gradient, and runs the BN backward on it: the
-    ATen ReLU / add / threshold-backward passes of the unfused block disappear."""
+    """Fused training-mode block tail ``act(BN(x) + res?)`` (BN statistics, normalisation,
+    residual add and ReLU / ReLU6 in one apply pass). The backward masks the gradient by the
+    forward's bit mask, returns it as the residual branch's gradient, and runs the BN backward on
+    it: the ATen ReLU / hardtanh / add / threshold-backward passes of the unfused block disappear.
+    ``act``: the kernels' activation code (0 none, 1 ReLU, 2 ReLU6); 0 defers to ``relu``."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, res, relu, pre=None, nbt=None, cr=0,
-                link=None):
+                link=None, act=0):
         T = ops.require()
         xh = _nhwc(x)
         rh = _nhwc(res) if res is not None else None
         w = weight.detach() if weight is not None else None
         b = bias.detach() if bias is not None else None
         # cr: the module's channels; x may carry more (a padded activation: zeros, kept zero)
+        act = int(act) if act else (1 if relu else 0)
         y, mean, invstd, mk = T.bn_train_fwd(xh, w, b, running_mean, running_var, float(eps), float(momentum), rh,
-                                             bool(relu), pre, nbt, int(cr))
+                                             act == 1, pre, nbt, int(cr), act)
+        if act == 2:
+            FUSE_COUNTS["bn_relu6"] += 1
         ctx.cr = int(cr)
         ctx.link = None
-        if link is not None and relu and xh.shape[-1] % 4 == 0:
+        if link is not None and act == 1 and xh.shape[-1] % 4 == 0:  # (the link fusions are ReLU-only)
             # detached: a link must not reference the graph (a node's ctx holds it: no cycle that would
             # keep old graphs — and their parameters' grad accumulators — alive)
             link.xh, link.mean, link.invstd, link.mk = xh.detach(), mean, invstd, mk
@@ -702,7 +715,7 @@ class _NativeBNAct(torch.autograd.Function):
             epochs.bump_stats()
         # the backward masks by the ReLU bit mask (1 byte per 4 channels) instead of re-reading y
         ctx.save_for_backward(xh, w if w is not None else torch.empty(0, device=x.device), mean, invstd, mk)
-        ctx.has_w, ctx.has_b, ctx.relu, ctx.has_res = weight is not None, bias is not None, relu, res is not None
+        ctx.has_w, ctx.has_b, ctx.act, ctx.has_res = weight is not None, bias is not None, act, res is not None
         return _as_nchw(y)
 
     @staticmethod
@@ -728,11 +741,11 @@ class _NativeBNAct(torch.autograd.Function):
             link.xh = link.mean = link.invstd = None
         dx, dgamma, dbeta, dres = T.bn_train_bwd(g, xh, w if ctx.has_w else None, mean, invstd,
                                                  ctx.needs_input_grad[0], None, want_res and not raw,
-                                                 mk if ctx.relu else None, ctx.cr, pre)
+                                                 mk if ctx.act else None, ctx.cr, pre, ctx.act)
         res_grad = (gy if raw else _as_nchw(dres)) if want_res else None
         return (_as_nchw(dx) if ctx.needs_input_grad[0] else None, dgamma if ctx.has_w else None,
                 dbeta if ctx.has_b else None, None, None, None, None, res_grad, None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 def _bn_counter(bn):
@@ -754,17 +767,27 @@ def _bn_fusable(bn, x, res=None) -> bool:
             and (res is None or (res.shape == x.shape and res.dtype == x.dtype and res.is_cuda)))
 
 
+def _act_code(m) -> int:
+    """The kernels' activation code of an activation module: 1 ReLU, 2 ReLU6 (0: neither)."""
+    return 1 if type(m) is nn.ReLU else 2 if type(m) is nn.ReLU6 else 0
+
+
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, res: torch.Tensor = None, relu: bool = True,
-           pre: torch.Tensor = None, link: _BNLink = None) -> torch.Tensor:
-    """``relu?(bn(x) + res?)`` — fused on the native kernels in training mode, the module's own
-    ops otherwise (eval mode, unsupported inputs). ``pre``: x's batch statistics already reduced
-    per tile by the producing conv's epilogue (:func:`conv_stats`), which skips the statistics
-    pass over x. ``link``: a residual block tail's :class:`_BNLink` (bottleneck backward fusions)."""
+           pre: torch.Tensor = None, link: _BNLink = None, act: int = None) -> torch.Tensor:
+    """``act(bn(x) + res?)`` — fused on the native kernels in training mode, the module's own
+    ops otherwise (eval mode, unsupported inputs). ``act``: the activation code (0 none, 1 ReLU,
+    2 ReLU6: ``min(max(v, 0), 6)``); ``relu`` picks between 0 and 1 when it is not given. ``pre``:
+    x's batch statistics already reduced per tile by the producing conv's epilogue
+    (:func:`conv_stats`), which skips the statistics pass over x. ``link``: a residual block
+    tail's :class:`_BNLink` (bottleneck backward fusions; ReLU tails only)."""
+    act = (1 if relu else 0) if act is None else int(act)
+    if act not in (0, 1, 2):
+        raise ValueError(f"bn_act: activation code {act} (0 none, 1 ReLU, 2 ReLU6)")
     if not _bn_fusable(bn, x, res):
         y = bn(_real(x, bn.num_features))
         if res is not None:
             y = y + _real(res, bn.num_features)
-        return F.relu(y) if relu else y
+        return F.relu(y) if act == 1 else F.relu6(y) if act == 2 else y
     momentum, nbt = bn.momentum, _bn_counter(bn)
     if nbt is None and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
@@ -775,7 +798,7 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, res: torch.Tensor = None, relu: 
     if pre is not None and (pre.dim() != 3 or pre.shape[2] != x.shape[1]):
         pre = None
     return _NativeBNAct.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, momentum if momentum is not None else 0.0, res,
-                              relu, pre, nbt, bn.num_features, link)
+                              act == 1, pre, nbt, bn.num_features, link if act == 1 else None, act)
 
 
 def _block_kind(m) -> str | None:
@@ -845,21 +868,25 @@ def _native_block_forward(self, x):
 
 
 # modules a padded activation (zeros past the real width) may pass through unchanged in meaning
+# (nn.ReLU6 with the fused MobileNet path, _MB_FUSE, only)
 _PAD_SAFE = (nn.ReLU, nn.MaxPool2d, nn.Dropout)
 
 
-def _native_sequential_forward(self, x):
+def _sequential_forward(self, x, mb):
     """nn.Sequential training forward fusing every (BatchNorm2d, ReLU) pair (VGG features). Native
     convs keep their carried output width through BN / ReLU / max-pool / dropout into the next
-    conv (no slice / pad copies at pruned widths); any other module gets the real width."""
+    conv (no slice / pad copies at pruned widths); any other module gets the real width.
+    ``mb`` (the MobileNet fusions, :data:`_MB_FUSE` when the forward was installed): (BatchNorm2d,
+    ReLU6) pairs fuse too, ReLU6 passes a padded activation on, and a native depthwise conv takes
+    the padded activation and keeps it padded."""
     mods = list(self.children())
     real = None  # real channel count while x is a padded activation
     i = 0
     while i < len(mods):
         m = mods[i]
-        if isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) \
-                and _bn_fusable(m, x):
-            x = bn_act(m, x, relu=True)
+        if isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and _bn_fusable(m, x) \
+                and (isinstance(mods[i + 1], nn.ReLU) or (mb and type(mods[i + 1]) is nn.ReLU6)):
+            x = bn_act(m, x, act=2 if type(mods[i + 1]) is nn.ReLU6 else 1)
             i += 2
             continue
         if "forward" in m.__dict__ and getattr(m.forward, "__func__", None) is _native_forward \
@@ -870,12 +897,30 @@ def _native_sequential_forward(self, x):
             real = m.out_channels if x.shape[1] != m.out_channels else None
             i += 1
             continue
+        if mb and "forward" in m.__dict__ and getattr(m.forward, "__func__", None) is _native_dw_forward \
+                and self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 \
+                and m.weight.dtype == torch.float32 and _dw_fits(m.weight, x, *_geom(m)):
+            _, s, p = _geom(m)
+            x = _NativeDWConv2d.apply(x, m.weight, m.bias, s, p)
+            real = m.weight.shape[0] if x.shape[1] != m.weight.shape[0] else None
+            i += 1
+            continue
         native_bn = "forward" in m.__dict__ and getattr(m.forward, "__func__", None) is _native_bn_forward
-        if real is not None and not (native_bn and _bn_fusable(m, x)) and type(m) not in _PAD_SAFE:
+        if real is not None and not (native_bn and _bn_fusable(m, x)) and type(m) not in _PAD_SAFE \
+                and not (mb and type(m) is nn.ReLU6):
             x, real = x[:, :real], None
         x = m(x)
         i += 1
     return x if real is None else x[:, :real]
+
+
+def _native_sequential_forward(self, x):
+    return _sequential_forward(self, x, True)
+
+
+def _native_sequential_forward_relu(self, x):
+    """:func:`_native_sequential_forward` as installed with the MobileNet fusions off."""
+    return _sequential_forward(self, x, False)
 
 
 def _native_resnet_forward(self, x):
@@ -982,7 +1027,10 @@ def _fits(conv: nn.Conv2d, x: torch.Tensor) -> bool:
 class _NativeDWConv2d(torch.autograd.Function):
     """Depthwise conv (depth multiplier 1) on the NHWC stencil kernels: the weight is read from
     the parameter in place (no pack), the gradients are deterministic gathers / ordered sums. The
-    channel count is the weight tensor's, not the module's metadata."""
+    channel count is the weight tensor's, not the module's metadata. ``x`` may be a carried
+    activation (more channels than the weight, a multiple of 4: the padding of a pruned width): the
+    output and the input gradient are carried too, with exact zeros past the weight's channels
+    whatever the padding holds, and the weight / bias gradients have the parameter's shapes."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad):
@@ -992,6 +1040,8 @@ class _NativeDWConv2d(torch.autograd.Function):
             w = w.contiguous()
         y = ops.require().dwconv_fwd(xh, w, bias.detach() if bias is not None else None, stride, pad)
         DW_COUNTS["fwd"] += 1
+        if xh.shape[3] > w.shape[0]:
+            FUSE_COUNTS["dw_carried"] += 1
         ctx.save_for_backward(xh, w)
         ctx.geom = (stride, pad, weight.stride(), bias is not None)
         return _as_nchw(y)
@@ -1018,9 +1068,9 @@ class _NativeDWConv2d(torch.autograd.Function):
 
 
 def _dw_fits(w: torch.Tensor, x: torch.Tensor, ks: int, s: int, p: int) -> bool:
-    B, C, H, W = x.shape
+    B, C, H, W = x.shape  # C: the weight's channel count, or the width an activation carries it at
     Ho, Wo = (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1
-    if not (C == w.shape[0] and B > 0 and H + 2 * p >= ks and W + 2 * p >= ks
+    if not (C in (w.shape[0], _act_w(w.shape[0])) and B > 0 and H + 2 * p >= ks and W + 2 * p >= ks
             and B * H * W * C * 4 <= _MAX_BYTES and B * Ho * Wo * C * 4 <= _MAX_BYTES):
         return False
     # the launchers' grid limit (2^24 blocks): one block per 256 (4-column strip, channel vector)
@@ -1032,13 +1082,121 @@ def _dw_fits(w: torch.Tensor, x: torch.Tensor, ks: int, s: int, p: int) -> bool:
 
 def _native_dw_forward(self, x):
     """Depthwise ``nn.Conv2d.forward`` on the native kernels. (A different function from
-    :func:`_native_forward`: containers that carry padded activations between dense convs hand a
-    depthwise conv the real-width slice, like any other module.)"""
+    :func:`_native_forward`: the containers that carry padded activations call
+    :class:`_NativeDWConv2d` themselves; the module takes and returns the real width.)"""
     ks, s, p = _geom(self)
     if not x.is_cuda or x.dtype != torch.float32 or self.weight.dtype != torch.float32 or x.dim() != 4 \
-            or not _dw_fits(self.weight, x, ks, s, p):
+            or x.shape[1] != self.weight.shape[0] or not _dw_fits(self.weight, x, ks, s, p):
         return type(self).forward(self, x)  # other dtypes / tensors beyond 2 GiB: the library path
     return _NativeDWConv2d.apply(x, self.weight, self.bias, s, p)
+
+
+def _ir_unit(u) -> bool:
+    return (type(u) is nn.Sequential and len(u) == 3 and isinstance(u[0], nn.Conv2d)
+            and isinstance(u[1], nn.BatchNorm2d) and type(u[2]) in (nn.ReLU6, nn.ReLU))
+
+
+def _ir_kind(m) -> str | None:
+    """Inverted-residual blocks (MobileNetV2; torchvision's and ``models/mobilenet.py``'s layout)
+    whose training forward can run fused: an attribute ``conv`` that is a plain ``nn.Sequential``
+    of ``[expand unit,] depthwise unit, Conv2d(1x1, stride 1, groups 1), BatchNorm2d`` with every
+    unit a plain ``nn.Sequential(Conv2d, BatchNorm2d, ReLU6 | ReLU)``, the last unit's conv
+    depthwise (:func:`dw_eligible`), the expand conv a dense native one (:func:`eligible`), and a
+    bool ``use_res_connect``. ``"expand"`` / ``"dw"`` (no expand unit), or None."""
+    conv = getattr(m, "conv", None)
+    if type(conv) is not nn.Sequential or not isinstance(getattr(m, "use_res_connect", None), bool):
+        return None
+    mods = list(conv)
+    if len(mods) not in (3, 4):
+        return None
+    *units, proj, bn = mods
+    if not all(_ir_unit(u) for u in units) or not dw_eligible(units[-1][0]):
+        return None
+    if len(units) == 2 and not eligible(units[0][0]):
+        return None
+    if not (isinstance(proj, nn.Conv2d) and eligible(proj) and _geom(proj) == (1, 1, 0)
+            and isinstance(bn, nn.BatchNorm2d)):
+        return None
+    return "expand" if len(units) == 2 else "dw"
+
+
+def _hooked(block) -> bool:
+    """Whether a module inside ``block`` has hooks, or global module hooks are registered: a fused
+    block forward does not call those modules, so it must not run then."""
+    mod = torch.nn.modules.module
+    if mod._global_forward_hooks or mod._global_forward_pre_hooks or mod._global_backward_hooks \
+            or mod._global_backward_pre_hooks:
+        return True
+    return any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks
+               for m in block.modules() if m is not block)
+
+
+class _Shape:
+    """Stand-in for an activation in the shape checks (:func:`_fits`, :func:`_dw_fits`)."""
+
+    def __init__(self, *shape):
+        self.shape = shape
+
+
+def _ir_plan(block, x):
+    """``(expand unit or None, depthwise unit, project conv, project BN)`` when every piece of the
+    block fits the fused flow for the input ``x``, else None."""
+    if _ir_kind(block) is None or _hooked(block):
+        return None
+    *units, proj, pbn = list(block.conv)
+    B, C, H, W = x.shape
+
+    def native(conv, fn):
+        return "forward" in conv.__dict__ and getattr(conv.forward, "__func__", None) is fn \
+            and conv.weight.dtype == torch.float32
+
+    def bn_ok(bn, c):  # _bn_fusable for an input of c channels
+        return bn.training and bn.num_features <= c and (bn.weight is None or bn.weight.dtype == torch.float32)
+
+    if len(units) == 2:
+        ec, ebn, _ = units[0]
+        ks, s, p = _geom(ec)
+        if not (native(ec, _native_forward) and ec.weight.shape[1] == C and _fits(ec, x)):
+            return None
+        C, H, W = _act_w(ec.weight.shape[0]), (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1
+        if not (bn_ok(ebn, C) and ebn.num_features == ec.weight.shape[0]):
+            return None
+    dc, dbn, _ = units[-1]
+    ks, s, p = _geom(dc)
+    cw = dc.weight.shape[0]
+    if not (native(dc, _native_dw_forward) and dbn.num_features == cw and bn_ok(dbn, C)
+            and (len(units) == 1 or units[0][0].weight.shape[0] == cw) and _dw_fits(dc.weight, _Shape(B, C, H, W), ks, s, p)):
+        return None
+    H, W = (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1
+    cout = proj.weight.shape[0]
+    if not (native(proj, _native_forward) and proj.weight.shape[1] == cw and _fits(proj, _Shape(B, C, H, W))
+            and bn_ok(pbn, cout) and pbn.num_features == cout and B * H * W > 0):
+        return None
+    if block.use_res_connect and tuple(x.shape) != (B, cout, H, W):
+        return None
+    return (units[0] if len(units) == 2 else None), units[-1], proj, pbn
+
+
+def _native_ir_forward(self, x):
+    """Inverted-residual training forward (:func:`_ir_kind`): the expand conv with epilogue BN
+    statistics, its fused BN + ReLU6 at the carried width, the depthwise conv on the carried
+    activation (float4 kernels at any pruned width, no slice / copy), its fused BN + ReLU6, the
+    project conv with epilogue statistics and one fused ``BN (+ shortcut)`` tail. Eval mode, other
+    inputs, pieces that do not fit and hooked modules take the module's own forward."""
+    plan = _ir_plan(self, x) if (self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) else None
+    if plan is None:
+        return type(self).forward(self, x)
+    expand, (dc, dbn, dact), proj, pbn = plan
+    FUSE_COUNTS["ir_block"] += 1
+    h = x
+    if expand is not None:
+        ec, ebn, eact = expand
+        y, part = conv_stats(ec, x, keep=True)
+        h = bn_act(ebn, y, pre=part, act=_act_code(eact))
+    _, s, p = _geom(dc)
+    h = bn_act(dbn, _NativeDWConv2d.apply(h, dc.weight, dc.bias, s, p), act=_act_code(dact))
+    y, part = conv_stats(proj, h)
+    return bn_act(pbn, y, res=x if self.use_res_connect else None, relu=False, pre=part)
 
 
 class _NativeDropout(torch.autograd.Function):
@@ -1100,7 +1258,15 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
     training mode — the fused BN / ReLU modules (and the convs run by a block's entry node or with
     epilogue BN statistics: a bottleneck's conv1 / downsample, every block's conv2 / conv3, the
     stem conv) are then not called, so forward hooks on them do not fire (attribution passes use
-    ``fuse=False``, eval-mode forwards are unchanged). Also switched: depthwise convs
+    ``fuse=False``, eval-mode forwards are unchanged). Inverted-residual blocks (:func:`_ir_kind`:
+    MobileNetV2) get a block forward that runs the expand conv, the depthwise conv, the project
+    conv and their BN + ReLU6 / BN (+ shortcut) tails fused, the hidden activation at its carried
+    width throughout; none of the modules inside such a block is called then (neither ``block.conv``
+    and its unit Sequentials nor their convs, BNs and ReLU6s), so the block falls back to its own
+    forward whenever one of them has a forward / backward hook or global module hooks exist (the
+    inner Sequentials keep their own forwards for that). ``(BatchNorm2d, ReLU6)`` pairs of any
+    other ``nn.Sequential`` fuse like ``(BatchNorm2d, ReLU)`` ones. ``TORCHPRUNER_FUSE_RELU6=0``
+    turns the ReLU6 fusions and the block forward off. Also switched: depthwise convs
     (:func:`dw_eligible`, the NHWC stencil kernels; ``TORCHPRUNER_NATIVE_DW=0`` leaves them on the
     library path), ``nn.Linear`` (MFMA GEMM), ``nn.MaxPool2d``,
     ``nn.AdaptiveAvgPool2d`` and, with ``dropout``, training-mode ``nn.Dropout`` (Philox masks
@@ -1113,17 +1279,24 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
         model.register_forward_pre_hook(epochs.bump_fwd)
         model._tp_pack_epoch_hook = True
     switched = []
+    inner = set()  # the Sequentials inside an inverted-residual block: they keep their own forwards
     for m in model.modules():
-        if "forward" in m.__dict__:
+        if "forward" in m.__dict__ or id(m) in inner:
             continue
-        if bn and fuse and _block_kind(m) is not None:
+        if bn and fuse and _MB_FUSE and _NATIVE_DW and _ir_kind(m) is not None:
+            # (containers before leaves: the block's convs and BNs are switched further down like any
+            # other leaf, so the block's fallback forward still runs them on the native kernels)
+            m.forward = types.MethodType(_native_ir_forward, m)
+            switched.append(m)
+            inner.update(id(c) for c in m.conv.modules() if type(c) is nn.Sequential)
+        elif bn and fuse and _block_kind(m) is not None:
             m.forward = types.MethodType(_native_block_forward, m)
             switched.append(m)
         elif bn and fuse and _is_resnet(m) and isinstance(m.relu, nn.ReLU) and isinstance(m.bn1, nn.BatchNorm2d):
             m.forward = types.MethodType(_native_resnet_forward, m)
             switched.append(m)
         elif bn and fuse and type(m) is nn.Sequential:
-            m.forward = types.MethodType(_native_sequential_forward, m)
+            m.forward = types.MethodType(_native_sequential_forward if _MB_FUSE else _native_sequential_forward_relu, m)
             switched.append(m)
         elif eligible(m):
             m.forward = types.MethodType(_native_forward, m)
