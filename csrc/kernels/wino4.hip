@@ -206,8 +206,13 @@ __device__ __forceinline__ void output_transform(const float (&m)[36], float (&y
 // Split-points epilogue, phase 1 (32-tile blocks of 4 waves): wave (grp = wave & 1, ph = wave >> 1)
 // holds rows 3ph..3ph+2 of the 6x6 transform-point grid (acc[nh * 18 + 6 rr + c]) for its 16
 // tiles x both 16-channel halves. Y = A^T M A is linear in M, so each wave forms the partial
-// output of its three rows; the ph = 0 waves write it into ya / yb, the ph = 1 waves add theirs
-// (read-modify-write; fixed order: one add per output after the write, deterministic). Partial column passes:
+// output of its three rows. The two waves of a tile group merge through ya / yb in two balanced
+// steps: each writes its partial of one channel half (ph 0: channels 0-15 into ya, ph 1: 16-31 into
+// yb), and after a barrier adds its partial of the other half onto its partner's (read-modify-
+// write). Every output is one write and one add, partner + own: a + b = b + a in IEEE arithmetic,
+// so the bits do not depend on which wave wrote first (deterministic). All four waves work in both
+// steps (ph 0 writing everything while ph 1 waited, then ph 1 adding everything while ph 0 waited,
+// put twice the LDS traffic and transform VALU on the block's critical path). Partial column passes:
 //   ph 0 (rows 0-2): t0 = m0 + m1 + m2, t1 = t3 = m1 - m2, t2 = m1 + m2
 //   ph 1 (rows 3-5): t0 = s, t1 = 2d, t2 = 4s, t3 = 8d + m5   (s = m3 + m4, d = m3 - m4)
 // and for ph 1 the row pass runs on s, d, m5 once each (at6 is linear), the scalings folding
@@ -216,66 +221,66 @@ __device__ __forceinline__ void at6row(const f2v* t, f2v& y0, f2v& y1, f2v& y2, 
   at6p(t[0], t[1], t[2], t[3], t[4], t[5], y0, y1, y2, y3);
 }
 
-// one wave's partial output (its three point rows) for tiles r, r + 1 of the lane: written
-// (ph 0) or added (ph 1) into the parked tile image
-template <int PH>
-__device__ __forceinline__ void sp_partial(const f32x4 (&acc)[NPT], int grp, int lane, float* ya, float* yb) {
+// one wave's partial output (its three point rows PH) of channel half NH for tiles r, r + 1 of
+// the lane: written (ADD = false) or added (ADD = true) into the parked tile image ybuf
+template <int PH, int NH, bool ADD>
+__device__ __forceinline__ void sp_partial(const f32x4 (&acc)[NPT], int grp, int lane, float* ybuf) {
   grp &= 1;  // tile group within the parked half of 32 tiles
   const int j = lane & 15, g = lane >> 4;
 #pragma unroll
-  for (int nh = 0; nh < 2; ++nh) {
-    float* ybuf = nh ? yb : ya;
+  for (int r = 0; r < 4; r += 2) {  // tiles r, r + 1 of this lane: packed pairs
+    const int tl = grp * 16 + 4 * g + r;
+    f2v m[18];
 #pragma unroll
-    for (int r = 0; r < 4; r += 2) {  // tiles r, r + 1 of this lane: packed pairs
-      const int tl = grp * 16 + 4 * g + r;
-      f2v m[18];
+    for (int x = 0; x < 18; ++x) m[x] = f2v{acc[NH * 18 + x][r], acc[NH * 18 + x][r + 1]};
+    float* dst = ybuf + tl * TPL + j;
+    f2v out[16];
+    if constexpr (PH == 0) {
+      f2v t0[6], t1[6], t2[6];
 #pragma unroll
-      for (int x = 0; x < 18; ++x) m[x] = f2v{acc[nh * 18 + x][r], acc[nh * 18 + x][r + 1]};
-      float* dst = ybuf + tl * TPL + j;
-      if constexpr (PH == 0) {
-        f2v t0[6], t1[6], t2[6];
+      for (int c = 0; c < 6; ++c) {
+        const f2v a = m[6 + c] + m[12 + c];
+        t1[c] = m[6 + c] - m[12 + c];
+        t2[c] = a;
+        t0[c] = m[c] + a;
+      }
+      f2v y[12];
+      at6row(t0, y[0], y[1], y[2], y[3]);
+      at6row(t1, y[4], y[5], y[6], y[7]);
+      at6row(t2, y[8], y[9], y[10], y[11]);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          const f2v a = m[6 + c] + m[12 + c];
-          t1[c] = m[6 + c] - m[12 + c];
-          t2[c] = a;
-          t0[c] = m[c] + a;
-        }
-        f2v y[12];
-        at6row(t0, y[0], y[1], y[2], y[3]);
-        at6row(t1, y[4], y[5], y[6], y[7]);
-        at6row(t2, y[8], y[9], y[10], y[11]);
+      for (int q = 0; q < 16; ++q) out[q] = y[q < 12 ? q : q - 8];  // output row 3 = row 1
+    } else {
+      f2v s[6], d[6];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const f2v v = y[q < 12 ? q : q - 8];  // output row 3 = row 1
-          dst[q * 16] = v.x;
-          dst[TPL + q * 16] = v.y;
-        }
+      for (int c = 0; c < 6; ++c) {
+        s[c] = m[c] + m[6 + c];
+        d[c] = m[c] - m[6 + c];
+      }
+      f2v ys[4], yd[4], y5[4];
+      at6row(s, ys[0], ys[1], ys[2], ys[3]);
+      at6row(d, yd[0], yd[1], yd[2], yd[3]);
+      at6row(m + 12, y5[0], y5[1], y5[2], y5[3]);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = q >> 2, col = q & 3;
+        if (row == 0) out[q] = ys[col];
+        else if (row == 1) out[q] = 2.f * yd[col];
+        else if (row == 2) out[q] = 4.f * ys[col];
+        else out[q] = 8.f * yd[col] + y5[col];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      if constexpr (ADD) {
+        // plain read-modify-write, one per output after the partner's write. NOT an LDS float
+        // atomic: ds_add_f32 made this epilogue 5x slower on post-ReLU operands than on N(0,1)
+        // ones (data-dependent; profiles/wino4/split_points_r5.txt)
+        dst[q * 16] += out[q].x;
+        dst[TPL + q * 16] += out[q].y;
       } else {
-        f2v s[6], d[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          s[c] = m[c] + m[6 + c];
-          d[c] = m[c] - m[6 + c];
-        }
-        f2v ys[4], yd[4], y5[4];
-        at6row(s, ys[0], ys[1], ys[2], ys[3]);
-        at6row(d, yd[0], yd[1], yd[2], yd[3]);
-        at6row(m + 12, y5[0], y5[1], y5[2], y5[3]);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int row = q >> 2, col = q & 3;
-          f2v add;
-          if (row == 0) add = ys[col];
-          else if (row == 1) add = 2.f * yd[col];
-          else if (row == 2) add = 4.f * ys[col];
-          else add = 8.f * yd[col] + y5[col];
-          // plain read-modify-write, one per output after the ph 0 write (fixed order). NOT an LDS
-          // float atomic: ds_add_f32 made this epilogue 5x slower on post-ReLU operands than on
-          // N(0,1) ones (data-dependent; profiles/wino4/split_points_r5.txt)
-          dst[q * 16] += add.x;
-          dst[TPL + q * 16] += add.y;
-        }
+        dst[q * 16] = out[q].x;
+        dst[TPL + q * 16] = out[q].y;
       }
     }
   }
@@ -285,35 +290,264 @@ __device__ __forceinline__ void sp_partial(const f32x4 (&acc)[NPT], int grp, int
 // their 64 tiles in two halves)
 __device__ __forceinline__ void sp_phase1(const f32x4 (&acc)[NPT], int ph, int grp, int lane, float* ya, float* yb,
                                           bool active) {
-  if (active && ph == 0) sp_partial<0>(acc, grp, lane, ya, yb);
-  __syncthreads();  // ph 1 adds after every ph 0 write has landed
-  if (active && ph == 1) sp_partial<1>(acc, grp, lane, ya, yb);
+  if (active) {
+    if (ph == 0) sp_partial<0, 0, false>(acc, grp, lane, ya);
+    else sp_partial<1, 1, false>(acc, grp, lane, yb);
+  }
+  __syncthreads();  // the adds follow every write
+  if (active) {
+    if (ph == 0) sp_partial<0, 1, true>(acc, grp, lane, yb);
+    else sp_partial<1, 0, true>(acc, grp, lane, ya);
+  }
+}
+
+// What one call's phase 2 has to produce, fixed where its inner loops are compiled (fp32 VALU does
+// not hide under the co-resident block's MFMAs, so work a call does not need is not issued):
+// PART the per-(image, channel) partial sums (APoZ counts / Taylor or Sensitivity terms), TAY the
+// data gradient's term (tay_term's modes), RELU the forward's activation, OUT / UNP the data
+// gradient's masked output, plain or unpooled through the argmax bytes. epilogue() selects the
+// instantiation with wave-uniform branches on the kernel arguments: the __global__ instantiations
+// stay as they were (the tuner's variants), each carries the phase-2 bodies its EPI can be asked for.
+template <bool PART_, int TAY_, bool RELU_, bool OUT_, bool UNP_>
+struct EpiCfg {
+  static constexpr bool PART = PART_, RELU = RELU_, OUT = OUT_, UNP = UNP_;
+  static constexpr int TAY = TAY_;
+};
+
+// Tile geometry of the epilogue of a block of NW waves x PPW accumulator sets (see epilogue()).
+// TPI: tiles of one image in a wave's phase-2 pass (its TPW consecutive tiles): their partial sums
+// are accumulated in registers and reduced across lanes once, into slot tb / TPI of ``part``; an
+// image's SPI slots are folded in a fixed order. The band geometry keeps one slot per tile (its
+// tile rows straddle images at no fixed period).
+template <int S, int NW, int PPW>
+struct EpiGeo {
+  static constexpr int TPR = (S + 3) / 4, TI = TPR * TPR;
+  static constexpr int GROUPS = NW * PPW / 2, TB = 16 * GROUPS, HALVES = TB / 32, TPW = 32 / NW;
+  static constexpr bool BAND = Band<S>::ON;
+  static constexpr int TBR = BAND ? Band<S>::TBR : TB;  // real tiles of the block (t0 = block * TBR)
+  static constexpr bool PART_TILE = S % 4 != 0;         // the last tile of a row is partial
+  static constexpr int TIB = TI < TB ? TI : TB;         // tiles of one image in this block
+  static constexpr int NIB = TB / TIB;                  // images in this block
+  static constexpr int TPI = BAND ? 1 : (TPW < TIB ? TPW : TIB);
+  static constexpr int SPI = TIB / TPI;
+  static_assert(TPI == 1 || TPI % 2 == 0, "pooled epilogue: a lane pair of tiles lies in one image");
+};
+
+// Phase 2 of the epilogue for the half ``hf`` of 32 parked tiles: coalesced traffic, 8 lanes cover
+// one pixel's 32 channels (128 B). The tile of a pass is wave-uniform, so its (image, row, column)
+// decomposition and element offset are scalar; a lane adds its own pixel / channel offset (32-bit
+// elements from the block's first image: a block spans a few images at most). apre / upre: the
+// data gradient's activations and argmax bytes of the lane's pixels, loaded before the barrier.
+// base + a lane's 32-bit element offset, formed as a 32-bit byte offset (block-local offsets are
+// far below 2^30 elements): a uniform base + 32-bit vector offset is one global store, no 64-bit VALU
+__device__ __forceinline__ float* eptr(float* base, unsigned elem) {
+  return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elem * 4u);
+}
+
+template <int EPI, int S, int NW, int PPW, typename CF>
+__device__ __forceinline__ void epi_phase2(const Args& p, int hf, int wave, int lane, int t0, int k0, const float* ya,
+                                           const float* yb, float* part, const f32x4 sc4, const f32x4 sh4,
+                                           const f32x4 (&apre)[EPI == BWD ? 32 / NW : 1][2],
+                                           const unsigned (&upre)[EPI == BWD ? 32 / NW : 1][2]) {
+  using E = EpiGeo<S, NW, PPW>;
+  constexpr int TPR = E::TPR, TI = E::TI, TPW = E::TPW, TPI = E::TPI;
+  const int c4 = lane & 7;
+  const int k = k0 + 4 * c4;
+  const unsigned KO = (unsigned)p.ko;
+  const bool kok = k < p.ko;
+  const unsigned b0 = (unsigned)t0 / TI, t0r = (unsigned)t0 % TI;  // first image, first tile within it
+  const float* ysrc = (c4 < 4 ? ya : yb) + (c4 & 3) * 4 + wave * (TPW * TPL);
+  const f2v sc01 = {sc4[0], sc4[1]}, sc23 = {sc4[2], sc4[3]}, sh01 = {sh4[0], sh4[1]}, sh23 = {sh4[2], sh4[3]};
+  (void)upre;
+  (void)apre;
+
+  if constexpr (EPI == FWD_POOL) {
+    constexpr int H = S / 2;
+    const int pp = (lane >> 3) & 3;  // pooled pixel (py, px) of the tile
+    const int py = pp >> 1, px = pp & 1;
+    const int hl = lane >> 5;  // lanes 32-63: the odd tile of a pair, the next one in its tile row
+                               // (2 pooled pixels on) or, S = 4, the next image
+    float* outb = p.out + (long long)b0 * (H * H) * KO;
+    uint8_t* amb = p.out_argmax + (long long)b0 * (H * H) * KO;
+    const unsigned lane_off = (unsigned)(py * H + px + hl * (S == 4 ? H * H : 2)) * KO + (unsigned)k;
+    ysrc += hl * TPL;
+    int cnt[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int tt = 0; tt < TPW / 2; ++tt) {
+      const int tbe = hf * 32 + wave * TPW + 2 * tt;  // the even tile of the pair
+      const unsigned rel = t0r + (unsigned)tbe, bl = rel / TI, ti = rel % TI, tr = ti / TPR, tc = ti % TPR;
+      if (t0 + tbe + hl < p.P) {
+        f32x4 best = {0.f, 0.f, 0.f, 0.f};
+        unsigned ae[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const int q = (2 * py + (w >> 1)) * 4 + 2 * px + (w & 1);
+          const f32x4 yv = *reinterpret_cast<const f32x4*>(ysrc + 2 * tt * TPL + q * 16);
+          const f2v v01 = f2v{yv[0], yv[1]} * sc01 + sh01, v23 = f2v{yv[2], yv[3]} * sc23 + sh23;
+          float v[4] = {v01.x, v01.y, v23.x, v23.y};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if constexpr (CF::RELU) v[e] = nan_relu(v[e]);
+            if constexpr (CF::PART) cnt[e] += v[e] > 0.f ? 1 : 0;
+            if (w == 0) {
+              best[e] = v[e];
+            } else {
+              // v > best, or the window's first NaN (v != v && best == best) — as two compares
+              // and a mask AND, no short-circuit: the lazy form compiled to a branch per element
+              const bool up = !(v[e] <= best[e]) & (best[e] == best[e]);
+              best[e] = up ? v[e] : best[e];
+              ae[e] = up ? (unsigned)w : ae[e];
+            }
+          }
+        }
+        if (kok) {
+          const unsigned o = ((bl * H + 2 * tr) * H + 2 * tc) * KO;  // scalar: the tile pair's first pixel
+          *reinterpret_cast<f32x4*>(eptr(outb + o, lane_off)) = best;
+          *reinterpret_cast<unsigned*>(amb + o + lane_off) = ae[0] | (ae[1] << 8) | (ae[2] << 16) | (ae[3] << 24);
+        }
+      }
+      if constexpr (CF::PART) {
+        if (TPI == 1 || (2 * tt + 2) % TPI == 0) {  // the image's last tile pair of this pass
+          // count over the 4 pooled pixels (lanes ^8, ^16) and, one image per pass, both tiles (^32)
+          f32x4 c;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            c[e] = xsum16(xsum8((float)cnt[e]));
+            if (TPI > 1) c[e] = xsum32(c[e]);
+            cnt[e] = 0;
+          }
+          const int slot = TPI == 1 ? tbe + hl : tbe / TPI;
+          if (pp == 0 && (TPI == 1 || hl == 0)) *reinterpret_cast<f32x4*>(part + slot * TK + 4 * c4) = c;
+        }
+      }
+    }
+  } else {
+    const int qq = lane >> 3;  // pixels qq and qq + 8 of the tile: (py, px) and (py + 2, px)
+    const int py = qq >> 2, px = qq & 3;
+    const unsigned lane_off = (unsigned)(py * S + px) * KO + (unsigned)k;
+    const unsigned h2_off = 2u * S * KO;
+    float* outb = nullptr;
+    if constexpr (EPI == FWD || (EPI == BWD && CF::OUT))
+      outb = p.out + (long long)b0 * ((CF::UNP ? 4 : 1) * S * S) * KO;
+    // unpooled output (2S x 2S): the window of pixel (y, x) starts at (2y, 2x)
+    const unsigned lane_off_u = (unsigned)(4 * py * S + 2 * px) * KO + (unsigned)k, h2_off_u = 8u * S * KO;
+    f2v s01 = {0.f, 0.f}, s23 = {0.f, 0.f};  // BWD partials of this lane over an image's tiles
+    float s4[4] = {0.f, 0.f, 0.f, 0.f};      // (Sensitivity: |g| is a scalar source modifier)
+    int cnt[4] = {0, 0, 0, 0};               // FWD: positive outputs
+#pragma unroll
+    for (int tt = 0; tt < TPW; ++tt) {
+      const int tb = hf * 32 + wave * TPW + tt;
+      const unsigned rel = t0r + (unsigned)tb, bl = rel / TI, ti = rel % TI, tr = ti / TPR, tc = ti % TPR;
+      if (t0 + tb < p.P && tb < E::TBR) {
+        const unsigned tile_off = ((bl * S + 4 * tr) * S + 4 * tc) * KO;
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          if (E::PART_TILE && (4 * (int)tr + py + 2 * h2 >= S || 4 * (int)tc + px >= S)) continue;  // outside the map
+          const f32x4 yv = *reinterpret_cast<const f32x4*>(ysrc + tt * TPL + (qq + 8 * h2) * 16);
+          const f2v y01 = {yv[0], yv[1]}, y23 = {yv[2], yv[3]};
+          if constexpr (EPI == PARTIAL) {
+            const int q = qq + 8 * h2;
+            const int b = (int)(b0 + bl), yy = 4 * (int)tr + (q >> 2), xx = 4 * (int)tc + (q & 3);
+            const long long pix = ((long long)b * S + yy) * S + xx;
+            const long long row = p.pool_order
+                                      ? ((((long long)b * (S / 2) + (yy >> 1)) * (S / 2) + (xx >> 1)) * 4 +
+                                         (yy & 1) * 2 + (xx & 1))
+                                      : pix;
+            *reinterpret_cast<f32x4*>(p.out + (long long)blockIdx.y * p.slab + row * p.K + k) = yv;
+          } else if constexpr (EPI == FWD) {
+            const f2v v01 = y01 * sc01 + sh01, v23 = y23 * sc23 + sh23;
+            f32x4 v = {v01.x, v01.y, v23.x, v23.y};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if constexpr (CF::RELU) v[e] = nan_relu(v[e]);
+              if constexpr (CF::PART) cnt[e] += v[e] > 0.f ? 1 : 0;
+            }
+            if (kok) *reinterpret_cast<f32x4*>(eptr(outb + tile_off, lane_off + h2 * h2_off)) = v;
+          } else {  // BWD
+            const f32x4 a = apre[EPI == BWD ? tt : 0][h2];
+            if constexpr (CF::PART) {
+              if constexpr (CF::TAY == 0) {  // Taylor -(g * a): one packed FMA per pair
+                s01 -= y01 * f2v{a[0], a[1]};
+                s23 -= y23 * f2v{a[2], a[3]};
+              } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s4[e] += CF::TAY == 1 ? fabsf(yv[e]) : (a[e] > 0.f ? fabsf(yv[e]) : 0.f);
+              }
+            }
+            if constexpr (CF::OUT) {
+              if (kok) {
+                const f2v m01 = y01 * sc01, m23 = y23 * sc23;
+                const float m[4] = {m01.x, m01.y, m23.x, m23.y};
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = a[e] > 0.f ? m[e] : 0.f;
+                if constexpr (CF::UNP) {  // the 2x2 window of this pooled pixel: v at its argmax, 0 elsewhere
+                  const unsigned am4 = upre[EPI == BWD ? tt : 0][h2];
+                  const unsigned ab[4] = {am4 & 0xffu, (am4 >> 8) & 0xffu, (am4 >> 16) & 0xffu, am4 >> 24};
+                  float* o00 = outb + ((bl * 2 * S + 8 * tr) * 2 * S + 8 * tc) * KO;
+                  const unsigned lo = lane_off_u + h2 * h2_off_u;
+#pragma unroll
+                  for (int w = 0; w < 4; ++w) {
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = ab[e] == (unsigned)w ? v[e] : 0.f;
+                    *reinterpret_cast<f32x4*>(eptr(o00, lo + (unsigned)((w >> 1) * 2 * S + (w & 1)) * KO)) = o;
+                  }
+                } else {
+                  *reinterpret_cast<f32x4*>(eptr(outb + tile_off, lane_off + h2 * h2_off)) = v;
+                }
+              }
+            }
+          }
+        }
+      }
+      if constexpr (CF::PART) {
+        if ((tt + 1) % TPI == 0) {  // the image's last tile of this pass: sum over its pixels, lanes ^8, ^16, ^32
+          f32x4 sum;
+          if constexpr (EPI == FWD) sum = f32x4{(float)cnt[0], (float)cnt[1], (float)cnt[2], (float)cnt[3]};
+          else if constexpr (CF::TAY == 0) sum = f32x4{s01.x, s01.y, s23.x, s23.y};
+          else sum = f32x4{s4[0], s4[1], s4[2], s4[3]};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            sum[e] = xsum32(xsum16(xsum8(sum[e])));
+            cnt[e] = 0;
+            s4[e] = 0.f;
+          }
+          s01 = s23 = f2v{0.f, 0.f};
+          if (qq == 0) *reinterpret_cast<f32x4*>(part + (tb / TPI) * TK + 4 * c4) = sum;
+        }
+      }
+    }
+  }
 }
 
 // Epilogue of a block of NW waves holding PPW (16-tile group, 16-channel half) accumulator sets
 // each: TB = 8 * NW * PPW tiles x 32 output channels. Virtual wave v = wave + NW * pp owns group
 // v % (TB/16) and half v / (TB/16) (PPW = 1: MODE 2/3; PPW = 2: the wide kernel, one wave = one
 // group x both halves). Outputs are staged in LDS per half of 32 tiles (ya: channels 0-15, yb:
-// 16-31), then coalesced 128-B traffic; ``part`` receives per-(tile, channel) partial sums
-// (TB x 32 floats). SPP: the split-points kernels (NW = 4 / 8: 32 / 64 tiles): phase 1 is sp_phase1.
+// 16-31), then coalesced 128-B traffic (epi_phase2); ``part`` receives the partial sums per (wave pass,
+// image, channel) (EpiGeo: TB / TPI slots x 32 floats, inside the TB x 32 buffer). SPP: the split-points kernels (NW = 4 / 8: 32 / 64 tiles): phase 1 is sp_phase1.
 template <int EPI, int S, int NW, int PPW = 1, bool SPP = false>
 __device__ __forceinline__ void epilogue(const Args& p, f32x4 (&acc)[PPW][NPT], int t0, int k0, float* ya, float* yb,
                                          float* part) {
-  constexpr int TPR = (S + 3) / 4, TI = TPR * TPR;
-  constexpr int GROUPS = NW * PPW / 2, TB = 16 * GROUPS, HALVES = TB / 32, TPW = 32 / NW;  // tiles per wave (phase 2)
-  constexpr bool BAND = Band<S>::ON;
-  constexpr int TBR = BAND ? Band<S>::TBR : TB;  // real tiles of the block (t0 = block * TBR)
-  constexpr bool PART_TILE = S % 4 != 0;         // the last tile of a row is partial
+  using E = EpiGeo<S, NW, PPW>;
+  constexpr int TPR = E::TPR, TI = E::TI, GROUPS = E::GROUPS, TB = E::TB, HALVES = E::HALVES;
+  constexpr int TPW = E::TPW;  // tiles per wave (phase 2)
+  constexpr bool BAND = E::BAND, PART_TILE = E::PART_TILE;
+  constexpr int TBR = E::TBR;
   static_assert(!BAND || (EPI != FWD_POOL && NW == 4 && PPW == 1), "band geometry: no pooling, 4-wave blocks");
   static_assert(!SPP || PPW == 1, "split-points epilogue: one accumulator set per wave");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the lane indices are re-derived from an opaque copy of the thread index: values shared with
+  // the kernel's prologue would stay live (or be spilled) across the whole main loop
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, g = lane >> 4;
   const bool want_part = EPI == BWD ? p.taylor != nullptr : p.apoz != nullptr;
   const int c4 = lane & 7;
   const int k = k0 + 4 * c4;
   const int KO = p.ko;          // output row width (pruned widths: K rounded up to 32 in the MFMAs only)
   const bool kok = k < KO;      // this lane's 4 channels are stored (KO % 4 == 0)
-  const float* ysrc = (c4 < 4 ? ya : yb) + (c4 & 3) * 4;
   f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
   if (p.scale && kok) sc4 = *reinterpret_cast<const f32x4*>(p.scale + k);
   if (EPI != BWD && p.shift && kok) sh4 = *reinterpret_cast<const f32x4*>(p.shift + k);
@@ -346,133 +580,69 @@ __device__ __forceinline__ void epilogue(const Args& p, f32x4 (&acc)[PPW][NPT], 
     // data gradient: this lane's phase-2 activations, issued before the barrier that ends phase 1
     // (the accumulators are dead, so the registers are free): their global-memory latency runs
     // while the block's other waves finish their output transforms, not inside phase 2
+    // (and, for the unpooled output, their argmax bytes). Buffer loads: the tile's element offset
+    // is the scalar offset, the lane's pixel / channel the vector offset, a lane without a pixel
+    // reads out of range (zeros) — no branch, no 64-bit address arithmetic, every load in flight
+    // at once. The host bounds the activation tensor to 2 GiB.
     f32x4 apre[EPI == BWD ? TPW : 1][2];
+    unsigned upre[EPI == BWD ? TPW : 1][2];
     if constexpr (EPI == BWD) {
-      const int qq = lane >> 3;
+      const unsigned elems = (unsigned)p.B * (S * S) * (unsigned)KO;
+      const i32x4 ars = make_rsrc(p.act, elems * 4u), urs = make_rsrc(p.unp, p.unp ? elems : 0u);
+      const bool has_unp = p.out != nullptr && p.unp != nullptr;
+      const int py = lane >> 5, px = (lane >> 3) & 3;  // pixels (py, px) and (py + 2, px) of the tile
+      const unsigned b0 = (unsigned)t0 / TI, t0r = (unsigned)t0 % TI;
+      const unsigned lane_off = (unsigned)(py * S + px) * (unsigned)KO + (unsigned)k, h2_off = 2u * S * (unsigned)KO;
 #pragma unroll
       for (int tt = 0; tt < TPW; ++tt) {
         const int tbv = hf * 32 + wave * TPW + tt;
-        const int pt = t0 + tbv;
-        const int b = pt / TI, ti = pt - b * TI, tr = ti / TPR, tc = ti - tr * TPR;
+        const unsigned rel = t0r + (unsigned)tbv, bl = rel / TI, ti = rel % TI, tr = ti / TPR, tc = ti % TPR;
+        const bool tile_ok = t0 + tbv < p.P && tbv < TBR;
+        const unsigned tile_off = (((b0 + bl) * S + 4 * tr) * S + 4 * tc) * (unsigned)KO;
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
-          const int q = qq + 8 * h2;
-          const int yy = 4 * tr + (q >> 2), xx = 4 * tc + (q & 3);
-          const long long pix = ((long long)b * S + yy) * S + xx;
-          const bool ok = kok && pt < p.P && tbv < TBR && (!PART_TILE || (yy < S && xx < S));
-          apre[tt][h2] = ok ? *reinterpret_cast<const f32x4*>(p.act + pix * KO + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-    }
-    __syncthreads();
-    // ---- phase 2: coalesced traffic; 8 lanes cover one pixel's 32 channels (128 B) ----------
-    if constexpr (EPI == FWD_POOL) {
-      const int pp = (lane >> 3) & 3;  // pooled pixel (py, px) of the tile
-      const int py = pp >> 1, px = pp & 1;
-#pragma unroll
-      for (int tt = 0; tt < TPW / 2; ++tt) {
-        const int tl = wave * TPW + 2 * tt + (lane >> 5);
-        const int tb = hf * 32 + tl;
-        const int pt = t0 + tb;
-        f32x4 cnt = {0.f, 0.f, 0.f, 0.f};
-        if (pt < p.P) {
-          f32x4 best = {0.f, 0.f, 0.f, 0.f};
-          unsigned arg = 0;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            const int q = (2 * py + (w >> 1)) * 4 + 2 * px + (w & 1);
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(ysrc + tl * TPL + q * 16);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float v = yv[e] * sc4[e] + sh4[e];
-              if (p.relu) v = nan_relu(v);
-              cnt[e] += v > 0.f ? 1.f : 0.f;
-              if (w == 0 || v > best[e] || (v != v && best[e] == best[e])) {
-                best[e] = v;
-                arg = (arg & ~(0xffu << (8 * e))) | ((unsigned)w << (8 * e));
-              }
-            }
-          }
-          const int b = pt / TI, ti = pt - b * TI, tr = ti / TPR, tc = ti - tr * TPR;
-          const long long o = (((long long)b * (S / 2) + 2 * tr + py) * (S / 2) + 2 * tc + px) * KO + k;
-          if (kok) {
-            *reinterpret_cast<f32x4*>(p.out + o) = best;
-            *reinterpret_cast<unsigned*>(p.out_argmax + o) = arg;
-          }
-        }
-        if (want_part) {  // per-(tile, channel) count over the 4 pooled pixels (lanes ^8, ^16)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            cnt[e] = xsum16(xsum8(cnt[e]));
-          }
-          if (pp == 0) *reinterpret_cast<f32x4*>(part + tb * TK + 4 * c4) = cnt;
+          const bool ok = kok && tile_ok && (!PART_TILE || (4 * (int)tr + py + 2 * h2 < S && 4 * (int)tc + px < S));
+          const unsigned off = lane_off + h2 * h2_off;
+          apre[tt][h2] = buf_load_f32x4(ars, (int)(ok ? off * 4u : OOB), (int)(tile_off * 4u), 0);
+          upre[tt][h2] = 0u;
+          if (has_unp) upre[tt][h2] = buf_load_u32(urs, (int)(ok ? off : OOB), (int)tile_off, 0);
         }
       }
     } else {
-      const int qq = lane >> 3;  // pixels qq and qq + 8 of the tile
-#pragma unroll
-      for (int tt = 0; tt < TPW; ++tt) {
-        const int tl = wave * TPW + tt;
-        const int tb = hf * 32 + tl;
-        const int pt = t0 + tb;
-        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-        if (pt < p.P && tb < TBR) {
-          const int b = pt / TI, ti = pt - b * TI, tr = ti / TPR, tc = ti - tr * TPR;
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            const int q = qq + 8 * h2;
-            if (PART_TILE && (4 * tr + (q >> 2) >= S || 4 * tc + (q & 3) >= S)) continue;  // outside the map
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(ysrc + tl * TPL + q * 16);
-            const long long pix = ((long long)b * S + 4 * tr + (q >> 2)) * S + 4 * tc + (q & 3);
-            if constexpr (EPI == PARTIAL) {
-              const int yy = 4 * tr + (q >> 2), xx = 4 * tc + (q & 3);
-              const long long row = p.pool_order
-                                        ? ((((long long)b * (S / 2) + (yy >> 1)) * (S / 2) + (xx >> 1)) * 4 +
-                                           (yy & 1) * 2 + (xx & 1))
-                                        : pix;
-              *reinterpret_cast<f32x4*>(p.out + (long long)blockIdx.y * p.slab + row * p.K + k) = yv;
-            } else if constexpr (EPI == FWD) {
-              f32x4 v;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                v[e] = yv[e] * sc4[e] + sh4[e];
-                if (p.relu) v[e] = nan_relu(v[e]);
-                sum[e] += v[e] > 0.f ? 1.f : 0.f;
-              }
-              if (kok) *reinterpret_cast<f32x4*>(p.out + pix * KO + k) = v;
-            } else {  // BWD
-              const f32x4 a = apre[EPI == BWD ? tt : 0][h2];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) sum[e] += tay_term(p.tay_mode, yv[e], a[e]);
-              if (p.out && kok) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = a[e] > 0.f ? yv[e] * sc4[e] : 0.f;
-                if (p.unp) {  // the 2x2 window of this pooled pixel: v at its argmax, 0 elsewhere
-                  const unsigned am4 = *reinterpret_cast<const unsigned*>(p.unp + pix * KO + k);
-                  const int yy = 4 * tr + (q >> 2), xx = 4 * tc + (q & 3);
-                  const long long o00 = (((long long)b * 2 * S + 2 * yy) * 2 * S + 2 * xx) * KO + k;
-#pragma unroll
-                  for (int w = 0; w < 4; ++w) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = ((am4 >> (8 * e)) & 0xffu) == (unsigned)w ? v[e] : 0.f;
-                    *reinterpret_cast<f32x4*>(p.out + o00 + ((long long)(w >> 1) * 2 * S + (w & 1)) * KO) = o;
-                  }
-                } else {
-                  *reinterpret_cast<f32x4*>(p.out + pix * KO + k) = v;
-                }
-              }
-            }
-          }
+      apre[0][0] = apre[0][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      upre[0][0] = upre[0][1] = 0u;
+    }
+    __syncthreads();
+    // ---- phase 2 (epi_phase2), specialised on what this call asks for: wave-uniform branches ----
+    auto run = [&](auto cf) {
+      epi_phase2<EPI, S, NW, PPW, decltype(cf)>(p, hf, wave, lane, t0, k0, ya, yb, part, sc4, sh4, apre, upre);
+    };
+    if constexpr (EPI == PARTIAL) {
+      run(EpiCfg<false, 0, false, true, false>{});
+    } else if constexpr (EPI == BWD) {
+      auto by_out = [&](auto pc, auto tc) {
+        constexpr bool PT = decltype(pc)::value;
+        constexpr int TM = decltype(tc)::value;
+        if (p.out == nullptr) {
+          if constexpr (PT) run(EpiCfg<PT, TM, false, false, false>{});  // (neither output nor partials: nothing to do)
+        } else if (!BAND && p.unp != nullptr) {
+          if constexpr (!BAND) run(EpiCfg<PT, TM, false, true, true>{});
+        } else {
+          run(EpiCfg<PT, TM, false, true, false>{});
         }
-        if (want_part) {  // per-(tile, channel) sum over the 16 pixels: lanes ^8, ^16, ^32 (fixed order)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            sum[e] = xsum32(xsum16(xsum8(sum[e])));
-          }
-          if (qq == 0) *reinterpret_cast<f32x4*>(part + tb * TK + 4 * c4) = sum;
-        }
+      };
+      using std::integral_constant;
+      if (!want_part) by_out(std::false_type{}, integral_constant<int, 0>{});
+      else if (p.tay_mode == 1) by_out(std::true_type{}, integral_constant<int, 1>{});
+      else if (p.tay_mode == 2) by_out(std::true_type{}, integral_constant<int, 2>{});
+      else by_out(std::true_type{}, integral_constant<int, 0>{});
+    } else {
+      if (want_part) {
+        if (p.relu) run(EpiCfg<true, 0, true, true, false>{});
+        else run(EpiCfg<true, 0, false, true, false>{});
+      } else {
+        if (p.relu) run(EpiCfg<false, 0, true, true, false>{});
+        else run(EpiCfg<false, 0, false, true, false>{});
       }
     }
     __syncthreads();  // ya / yb are rewritten by the next half
@@ -499,19 +669,20 @@ __device__ __forceinline__ void epilogue(const Args& p, f32x4 (&acc)[PPW][NPT], 
     }
     return;
   }
-  // ---- per-(image, channel) sums over the block's tiles of the image, fixed order ------------
+  // ---- per-(image, channel) sums over the image's SPI slots of ``part`` (one per wave pass that
+  // held tiles of the image, each already summed over those tiles), fixed order ----------------
   // Whole images per block: one writer per sum. A block of half an image (S = 32, 32 tiles):
   // Taylor partials go to slot (half) of the (R, B, K) slab (single writer per slot); APoZ counts
   // are exact integers, so their float atomic adds are order-independent.
-  constexpr int TIB = TI < TB ? TI : TB;  // tiles of one image in this block
-  constexpr int NIB = TB / TIB;           // images in this block
+  constexpr int NIB = E::NIB, SPI = E::SPI;
   const int b0 = t0 / TI;
   for (int t = tid; t < NIB * TK; t += 64 * NW) {
     const int il = t / TK, kk = t - il * TK;
     const int b = b0 + il;
     if (b >= p.B || k0 + kk >= KO) continue;
     float s = 0.f;
-    for (int ti = 0; ti < TIB; ++ti) s += part[(il * TIB + ti) * TK + kk];
+#pragma unroll
+    for (int si = 0; si < SPI; ++si) s += part[(il * SPI + si) * TK + kk];
     constexpr bool split_img = TI > TB;
     if constexpr (EPI == BWD) {
       const int slot = split_img ? (t0 / TB) % (TI / TB) : 0;
