@@ -420,6 +420,101 @@ c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x
   return db;
 }
 
+void check_dwa_params(const at::Tensor& w, const at::Tensor& scale, const at::Tensor* shift, int64_t C,
+                      const at::Tensor& like) {
+  check_cuda_f32(w, "w");
+  check_cuda_f32(scale, "scale");
+  TORCH_CHECK(C % 4 == 0, "dwconv_act needs a channel count that is a multiple of 4 (pad the channels), got ", C);
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == w.size(3) && w.is_contiguous() &&
+                  w.device() == like.device(), "w must be a contiguous (C, 1, k, k) depthwise weight");
+  TORCH_CHECK(scale.dim() == 1 && scale.size(0) == C && scale.is_contiguous() && scale.device() == like.device(),
+              "scale must be a contiguous (C,) tensor");
+  if (shift != nullptr) {
+    check_cuda_f32(*shift, "shift");
+    TORCH_CHECK(shift->dim() == 1 && shift->size(0) == C && shift->is_contiguous() && shift->device() == like.device(),
+                "shift must be a contiguous (C,) tensor");
+  }
+}
+
+void check_dwa_acts(int64_t in_act, int64_t out_act) {
+  TORCH_CHECK(in_act >= 0 && in_act <= 2 && out_act >= 0 && out_act <= 2,
+              "activation codes are 0 (none), 1 (ReLU), 2 (ReLU6), got ", in_act, " / ", out_act);
+}
+
+// y = out_act(scale * dwconv(in_act(x)) + shift) on NHWC tensors; apoz (B, C) += count(y > 0)
+at::Tensor dwconv_act_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
+                          int64_t s, int64_t pad, int64_t in_act, int64_t out_act,
+                          const c10::optional<at::Tensor>& apoz) {
+  check_cuda_f32(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "x must be a non-empty contiguous NHWC tensor");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  check_dwa_params(w, scale, &shift, C, x);
+  check_dwa_acts(in_act, out_act);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  TORCH_CHECK(x.numel() < (int64_t(1) << 29), "x exceeds the kernels' 2 GiB operand range");
+  float* ap = nullptr;
+  if (apoz.has_value() && apoz->defined()) {
+    check_cuda_f32(*apoz, "apoz");
+    TORCH_CHECK(apoz->dim() == 2 && apoz->size(0) == B && apoz->size(1) == C && apoz->is_contiguous() &&
+                    apoz->device() == x.device(), "apoz must be a contiguous (B, C) tensor");
+    ap = apoz->data_ptr<float>();
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty({B, (H + 2 * pad - k) / s + 1, (W + 2 * pad - k) / s + 1, C}, x.options());
+  TP_CHECK_HIP(tp_dwconv_act_fwd(x.data_ptr<float>(), w.data_ptr<float>(), scale.data_ptr<float>(),
+                                 shift.data_ptr<float>(), y.data_ptr<float>(), ap, (int)B, (int)H, (int)W, (int)C,
+                                 (int)k, (int)s, (int)pad, (int)in_act, (int)out_act, cur_stream()));
+  return y;
+}
+
+int64_t dwconv_act_tay_slots(int64_t H, int64_t W, int64_t C) {
+  TORCH_CHECK(H > 0 && W > 0 && C > 0 && H < (int64_t(1) << 29) && W < (int64_t(1) << 29) && C < (int64_t(1) << 29),
+              "bad shape");
+  return tp_dwconv_act_tay_slots((int)H, (int)W, (int)C);
+}
+
+// dz = mask_in(z) * dA, dA = dwconv^T(mask_out(y) * g * scale); tay: zeroed (R, B, C) slab of the
+// partial sums of -(dA * in_act(z)) (tay_mode 0) or |dA| (1), R = dwconv_act_tay_slots(H, W, C)
+at::Tensor dwconv_act_dgrad(const at::Tensor& g, const at::Tensor& y, const at::Tensor& w, const at::Tensor& scale,
+                            const at::Tensor& z, int64_t H, int64_t W, int64_t s, int64_t pad, int64_t in_act,
+                            int64_t out_act, const c10::optional<at::Tensor>& tay, int64_t tay_mode) {
+  check_cuda_f32(g, "g");
+  check_cuda_f32(y, "y");
+  check_cuda_f32(z, "z");
+  TORCH_CHECK(z.dim() == 4 && z.is_contiguous() && z.numel() > 0 && z.size(1) == H && z.size(2) == W,
+              "z must be a non-empty contiguous (B, H, W, C) tensor");
+  const int64_t B = z.size(0), C = z.size(3);
+  check_dwa_params(w, scale, nullptr, C, z);
+  check_dwa_acts(in_act, out_act);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+  TORCH_CHECK(g.dim() == 4 && g.is_contiguous() && g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo &&
+                  g.size(3) == C && g.device() == z.device(), "g must be a contiguous (B, Ho, Wo, C) tensor");
+  TORCH_CHECK(y.sizes() == g.sizes() && y.is_contiguous() && y.device() == z.device(), "y must match g");
+  TORCH_CHECK(z.numel() < (int64_t(1) << 29), "z exceeds the kernels' 2 GiB operand range");
+  float* tp = nullptr;
+  int R = 0;
+  if (tay.has_value() && tay->defined()) {
+    check_cuda_f32(*tay, "tay");
+    TORCH_CHECK(tay_mode == 0 || tay_mode == 1, "tay_mode is 0 (Taylor) or 1 (Sensitivity)");
+    R = tp_dwconv_act_tay_slots((int)H, (int)W, (int)C);
+    TORCH_CHECK(tay->dim() == 3 && tay->size(0) == R && tay->size(1) == B && tay->size(2) == C &&
+                    tay->is_contiguous() && tay->device() == z.device(),
+                "tay must be a contiguous (dwconv_act_tay_slots(H, W, C), B, C) slab");
+    TORCH_CHECK(tay->numel() < (int64_t(1) << 29), "tay exceeds the kernels' 2 GiB operand range");
+    tp = tay->data_ptr<float>();
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto dz = at::empty_like(z);
+  TP_CHECK_HIP(tp_dwconv_act_dgrad(g.data_ptr<float>(), y.data_ptr<float>(), w.data_ptr<float>(),
+                                   scale.data_ptr<float>(), z.data_ptr<float>(), dz.data_ptr<float>(), tp, R,
+                                   (int)tay_mode, (int)B, (int)H, (int)W, (int)C, (int)k, (int)s, (int)pad,
+                                   (int)in_act, (int)out_act, cur_stream()));
+  return dz;
+}
+
 at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
   check_cuda_f32(g_, "g");
   auto g = g_.contiguous();
@@ -452,6 +547,11 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("dwconv_fwd(Tensor x, Tensor w, Tensor? bias, int stride, int pad) -> Tensor");
   m.def("dwconv_dgrad(Tensor g, Tensor w, int H, int W, int stride, int pad) -> Tensor");
   m.def("dwconv_wgrad(Tensor g, Tensor x, int k, int stride, int pad, Tensor(a!) dw, bool want_bias) -> Tensor?");
+  m.def("dwconv_act_fwd(Tensor x, Tensor w, Tensor scale, Tensor shift, int stride, int pad, int in_act, int out_act, "
+        "Tensor(a!)? apoz=None) -> Tensor");
+  m.def("dwconv_act_dgrad(Tensor g, Tensor y, Tensor w, Tensor scale, Tensor z, int H, int W, int stride, int pad, "
+        "int in_act, int out_act, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
+  m.def("dwconv_act_tay_slots(int H, int W, int C) -> int", &dwconv_act_tay_slots);
   register_engine_ops_def(m);
 }
 
@@ -474,5 +574,7 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("dwconv_fwd", &dwconv_fwd);
   m.impl("dwconv_dgrad", &dwconv_dgrad);
   m.impl("dwconv_wgrad", &dwconv_wgrad);
+  m.impl("dwconv_act_fwd", &dwconv_act_fwd);
+  m.impl("dwconv_act_dgrad", &dwconv_act_dgrad);
   register_engine_ops_impl(m);
 }

@@ -49,6 +49,14 @@ hipError_t tp_dwconv_dgrad_cw(const float* g, const float* w, float* dx, int B, 
 hipError_t tp_dwconv_wgrad_cw(const float* g, const float* x, float* dw, float* db, double* ws, int chunks, int B,
                               int H, int W, int C, int Cw, int k, int s, int pad, long long s0, long long s2,
                               long long s3, hipStream_t st);
+// dwconv_act.hip (C % 4 == 0; activation codes 0 none, 1 ReLU, 2 ReLU6)
+hipError_t tp_dwconv_act_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
+                             float* apoz, int B, int H, int W, int C, int k, int s, int pad, int in_act, int out_act,
+                             hipStream_t st);
+int tp_dwconv_act_tay_slots(int H, int W, int C);
+hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
+                               float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
+                               int pad, int in_act, int out_act, hipStream_t st);
 // data_ops.hip
 hipError_t tp_augment_u8(const uint8_t* src, const int64_t* idx, const int* aug, int B, int C, int H, int W, int pad,
                          const float* mean, const float* inv_std, float* out, hipStream_t st);

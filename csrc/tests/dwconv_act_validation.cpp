@@ -1,0 +1,158 @@
+// Host-side validation of the fused depthwise-conv launchers (csrc/kernels/dwconv_act.hip), built
+// with AddressSanitizer + UBSan on the host code like dwconv_validation.cpp. Both launchers must
+// reject, BEFORE touching the GPU, an unsupported kernel size / stride / padding / activation code,
+// a channel count that is no multiple of 4, an empty output, missing or misaligned operands,
+// operands of 2^31 bytes or more and a partial slab whose slot count is not the helper's; the slot
+// helper must stay in range over every (H, W, C). Runs on a CPU-only machine: no kernel is launched.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+
+extern "C" {
+hipError_t tp_dwconv_act_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
+                             float* apoz, int B, int H, int W, int C, int k, int s, int pad, int in_act, int out_act,
+                             hipStream_t st);
+int tp_dwconv_act_tay_slots(int H, int W, int C);
+hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
+                               float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
+                               int pad, int in_act, int out_act, hipStream_t st);
+}
+
+static int failures = 0;
+#define EXPECT(cond)                                                   \
+  do {                                                                 \
+    if (!(cond)) {                                                     \
+      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
+      ++failures;                                                      \
+    }                                                                  \
+  } while (0)
+
+static float* const A16 = reinterpret_cast<float*>(64);  // aligned, never dereferenced
+static float* const A4 = reinterpret_cast<float*>(68);
+
+static bool fwd_rejects(int B, int H, int W, int C, int k, int s, int pad, int ia = 2, int oa = 2) {
+  return tp_dwconv_act_fwd(A16, A16, A16, A16, A16, A16, B, H, W, C, k, s, pad, ia, oa, nullptr) ==
+         hipErrorInvalidValue;
+}
+static bool dgrad_rejects(int B, int H, int W, int C, int k, int s, int pad, int ia = 2, int oa = 2) {
+  const int R = tp_dwconv_act_tay_slots(H, W, C);
+  return tp_dwconv_act_dgrad(A16, A16, A16, A16, A16, A16, nullptr, 0, 0, B, H, W, C, k, s, pad, ia, oa, nullptr) ==
+             hipErrorInvalidValue &&
+         tp_dwconv_act_dgrad(A16, A16, A16, A16, A16, A16, A16, R, 0, B, H, W, C, k, s, pad, ia, oa, nullptr) ==
+             hipErrorInvalidValue;
+}
+static bool both_reject(int B, int H, int W, int C, int k, int s, int pad, int ia = 2, int oa = 2) {
+  return fwd_rejects(B, H, W, C, k, s, pad, ia, oa) && dgrad_rejects(B, H, W, C, k, s, pad, ia, oa);
+}
+
+int main() {
+  // unsupported kernel size, stride, padding
+  EXPECT(both_reject(2, 8, 8, 16, 1, 1, 0));
+  EXPECT(both_reject(2, 8, 8, 16, 4, 1, 1));
+  EXPECT(both_reject(2, 8, 8, 16, 7, 1, 3));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 0, 1));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 3, 1));
+  EXPECT(both_reject(2, 8, 8, 16, 5, 4, 2));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 1, -1));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 1, 3));  // pad > k - 1
+  EXPECT(both_reject(2, 8, 8, 16, 5, 2, 5));
+  // activation codes outside 0..2
+  EXPECT(both_reject(2, 8, 8, 16, 3, 1, 1, 3, 2));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 1, 1, 2, -1));
+  EXPECT(both_reject(2, 8, 8, 16, 3, 1, 1, 2147483647, 0));
+  // channel counts that are no multiple of 4 (the engine pads)
+  EXPECT(both_reject(2, 8, 8, 67, 3, 1, 1));
+  EXPECT(both_reject(2, 8, 8, 2, 3, 1, 1));
+  EXPECT(both_reject(2, 8, 8, 0, 3, 1, 1));
+  EXPECT(both_reject(2, 8, 8, -4, 3, 1, 1));
+  // empty tensors / empty output
+  EXPECT(both_reject(0, 8, 8, 16, 3, 1, 1));
+  EXPECT(both_reject(2, 0, 8, 16, 3, 1, 1));
+  EXPECT(both_reject(2, 8, -3, 16, 3, 1, 1));
+  EXPECT(both_reject(2, 2, 8, 16, 3, 1, 0));  // H + 2 pad < k
+  EXPECT(both_reject(2, 8, 2, 16, 5, 2, 1));  // W + 2 pad < k
+  // operands of 2^31 bytes or more (and arguments whose products overflow 32 / 64 bits)
+  EXPECT(both_reject(128, 256, 256, 64, 3, 1, 1));  // exactly 2^31 bytes
+  EXPECT(both_reject(4096, 256, 256, 68, 3, 2, 1));
+  EXPECT(both_reject(2147483647, 2147483647, 2147483647, 2147483644, 3, 1, 1));
+  EXPECT(both_reject(1, 2147483647, 1, 4, 3, 1, 1));
+  EXPECT(both_reject(1, 1, 1, 2147483644, 3, 1, 1));
+  // shapes below 2^31 bytes that would need more 256-thread blocks than a grid takes
+  EXPECT(both_reject(1 << 12, 1 << 13, 1, 4, 3, 1, 1));
+  // missing and misaligned operands, one at a time
+  float* n = nullptr;
+#define FWD(x, w, sc, sh, y, ap) tp_dwconv_act_fwd(x, w, sc, sh, y, ap, 2, 8, 8, 16, 3, 1, 1, 2, 2, nullptr)
+  EXPECT(FWD(n, A16, A16, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, n, A16, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, n, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A16, n, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A16, A16, n, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A4, A16, A16, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A4, A16, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A4, A16, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A16, A4, A16, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A16, A16, A4, n) == hipErrorInvalidValue);
+  EXPECT(FWD(A16, A16, A16, A16, A16, A4) == hipErrorInvalidValue);
+#undef FWD
+  const int R = tp_dwconv_act_tay_slots(8, 8, 16);
+  EXPECT(R == 8);
+#define DG(g, y, w, sc, z, dz, tay, r, mode, oa) \
+  tp_dwconv_act_dgrad(g, y, w, sc, z, dz, tay, r, mode, 2, 8, 8, 16, 5, 2, 2, 2, oa, nullptr)
+  EXPECT(DG(n, A16, A16, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, n, A16, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);  // y is read when out_act != 0
+  EXPECT(DG(A16, A16, n, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, n, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, n, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, n, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A4, A16, A16, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A4, A16, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A4, A16, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A4, A16, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A4, A16, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A4, n, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A4, R, 0, 2) == hipErrorInvalidValue);
+  // the partial slab: a slot count that is not the helper's, a bad mode
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A16, R + 1, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A16, R - 1, 1, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A16, 0, 0, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A16, R, 2, 2) == hipErrorInvalidValue);
+  EXPECT(DG(A16, A16, A16, A16, A16, A16, A16, R, -1, 2) == hipErrorInvalidValue);
+#undef DG
+  // a slab of 2^31 bytes or more although z is below it: 1 x 8192 x 4 x 16380 floats of z (2^31 - 2^19
+  // bytes... the slab has H * ceil(W/4 * C/4 / 256) = 8192 * 16 slots of C floats per image)
+  {
+    const int H = 8192, W = 4, C = 16380, B = 1;
+    const int r = tp_dwconv_act_tay_slots(H, W, C);
+    EXPECT(r == H * 16);
+    EXPECT((long long)B * H * W * C * 4 < (1ll << 31) && (long long)r * B * C * 4 >= (1ll << 31));
+    EXPECT(tp_dwconv_act_dgrad(A16, A16, A16, A16, A16, A16, A16, r, 0, B, H, W, C, 3, 1, 1, 2, 2, nullptr) ==
+           hipErrorInvalidValue);
+  }
+
+  // slot helper: 0 for shapes the kernels reject, else one slot per (row, 256-thread slice): at least
+  // H, and the slab of one image never more than a few times the activation
+  for (int h = 1; h <= 300; h = h < 20 ? h + 1 : h + h / 5)
+    for (int w = 1; w <= 300; w = w < 40 ? w + 1 : w + w / 6)
+      for (int c = 1; c <= 4096; c = c < 70 ? c + 1 : c + c / 9 + 1) {
+        const int r = tp_dwconv_act_tay_slots(h, w, c);
+        if (c % 4) {
+          EXPECT(r == 0);
+          continue;
+        }
+        const long long q = (long long)((w + 3) / 4) * (c / 4);
+        EXPECT(r == h * (int)((q + 255) / 256));
+        EXPECT(r >= h && (long long)r * 256 < (long long)h * (q + 256));
+      }
+  EXPECT(tp_dwconv_act_tay_slots(0, 16, 16) == 0 && tp_dwconv_act_tay_slots(16, -4, 16) == 0);
+  EXPECT(tp_dwconv_act_tay_slots(16, 16, -8) == 0 && tp_dwconv_act_tay_slots(16, 16, 2) == 0);
+  EXPECT(tp_dwconv_act_tay_slots(2147483647, 2147483647, 2147483644) == 0);  // no overflow, out of range
+  EXPECT(tp_dwconv_act_tay_slots(1 << 20, 4, 4) == (1 << 20));
+
+  if (failures) {
+    std::fprintf(stderr, "%d failure(s)\n", failures);
+    return 1;
+  }
+  std::printf("dwconv_act validation ok\n");
+  return 0;
+}

@@ -252,6 +252,30 @@ def build_dwconv_sanitizer(verbose: bool = False) -> Path:
     return exe
 
 
+def build_dwconv_act_sanitizer(verbose: bool = False) -> Path:
+    """Build ``csrc/tests/dwconv_act_validation.cpp`` against the fused depthwise-conv launchers
+    (``dwconv_act.hip``) with AddressSanitizer + UBSan on the HOST code only, like
+    :func:`build_dwconv_sanitizer`. Returns the executable path."""
+    out_dir = ROOT / "build" / "asan"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    headers = sorted((CSRC / "include").glob("*.h"))
+    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    src, obj = CSRC / "kernels" / "dwconv_act.hip", out_dir / "dwconv_act.o"
+    test_src, test_obj = CSRC / "tests" / "dwconv_act_validation.cpp", out_dir / "dwconv_act_validation.o"
+    jobs = []
+    if _needs_rebuild(src, obj, headers):
+        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
+                     "-c", src, "-o", obj])
+    if _needs_rebuild(test_src, test_obj, headers):
+        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
+    with ThreadPoolExecutor(max_workers=2) as ex:
+        list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / "dwconv_act_validation"
+    if jobs or not exe.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
+    return exe
+
+
 def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
     """Build ``csrc/tests/dwconv_carried_validation.cpp`` against the carried-width depthwise-conv
     launchers (``dwconv.hip``) and the BatchNorm launchers (``batchnorm.hip``) with

@@ -134,7 +134,7 @@ class _AttributionMetric(ABC):
     """Abstract base of every metric (reference attributions.py:15-25)."""
 
     def __init__(self, model, data_generator, criterion, device, reduction="mean", *, group=None,
-                 shard_data=None, checkpoint=None, checkpoint_every=50, compute_dtype=None):
+                 shard_data=None, checkpoint=None, checkpoint_every=50, compute_dtype=None, mobilenet_engine=None):
         assert reduction in ["mean", "none", "sum"] or callable(reduction), \
             'Reduction must be a string in ["mean", "none", "sum"] or a function'
         self.model = model
@@ -158,6 +158,9 @@ class _AttributionMetric(ABC):
         assert compute_dtype in (None, torch.float32, torch.bfloat16, torch.float16), \
             "compute_dtype must be None, torch.float32, torch.bfloat16 or torch.float16"
         self.compute_dtype = compute_dtype
+        # MobileNet engine (engine/mobilenet_engine.py): opt-in. None reads TORCHPRUNER_MOBILENET_ENGINE
+        # (default 0); APoZ / Taylor / Sensitivity then try fused -> resnet -> mobilenet -> generic
+        self.mobilenet_engine = mobilenet_engine
         self._ckpt = None
         self._run_accs = None
         self._peeked = None  # (first batch, live iterator) taken by _first_input_shape
@@ -261,7 +264,8 @@ class _AttributionMetric(ABC):
 
     def _record_path(self, path: str, eval_modules, why=()):
         """Remember and log (once per run, ``torchpruner`` logger) which path served it:
-        ``fused`` (VGG-chain engine), ``resnet`` (ResNet engine) or ``generic`` (PyTorch
+        ``fused`` (VGG-chain engine), ``resnet`` (ResNet engine), ``mobilenet`` (MobileNet engine,
+        opt-in) or ``generic`` (PyTorch
         modules + HIP reduction kernels), with the engines' rejection reasons."""
         names = {id(m): n for n, m in self.model.named_modules()}
         mods = [names.get(id(m), type(m).__name__) for m in eval_modules]
@@ -560,6 +564,20 @@ class _AttributionMetric(ABC):
             return _reject(why, f"compute_dtype={self.compute_dtype} runs the generic autocast path")
         return maybe_resnet_engine(self.model, eval_modules, self.device, grad=True, why=why)
 
+    def _mobilenet_engine(self, eval_modules, why=None, grad=False):
+        """The MobileNet engine when it is switched on (the ``mobilenet_engine`` keyword, else
+        ``TORCHPRUNER_MOBILENET_ENGINE``) and serves ``eval_modules`` (eval-mode torchvision-layout
+        MobileNetV2, block ReLU6s; any differentiable criterion), else None. Switched off, it
+        leaves no rejection reason: the path is then exactly the one without it."""
+        from ..engine.fused_chain import _reject
+        from ..engine.mobilenet_engine import maybe_mobilenet_engine, mobilenet_engine_default
+        on = mobilenet_engine_default() if self.mobilenet_engine is None else bool(self.mobilenet_engine)
+        if not on:
+            return None
+        if not self._engines_allowed():
+            return _reject(why, f"compute_dtype={self.compute_dtype} runs the generic autocast path")
+        return maybe_mobilenet_engine(self.model, eval_modules, self.device, grad=grad, why=why)
+
     def _fused_engine(self, eval_modules, why=None, need_ce=True, pre_act_ok=False):
         """The fused chain engine (engine, block indices) for ``eval_modules``, else None.
         ``compute_dtype=torch.bfloat16`` runs it with bf16-operand 3x3 convs (fp32 accumulation,
@@ -615,15 +633,19 @@ class _AttributionMetric(ABC):
 
     def _resnet_grad_pass(self, eng, eval_modules, accs, mode):
         """Per batch: one engine forward + input-gradient backward scores every module; the
-        (B, C_padded) slabs are folded into fp64 accumulators (16 layers per launch)."""
+        (B, C_padded) slabs are folded into fp64 accumulators (16 layers per launch). Serves the
+        ResNet engine (BN evaluation modules: ``num_features`` wide, two batches in flight) and
+        the MobileNet engine (ReLU6 evaluation modules: ``eng.real_width``, one batch at a time)."""
         from ..engine.fused_chain import engine_criterion
+        width = getattr(eng, "real_width", None) or (lambda m: m.num_features)
         uniq = list(dict.fromkeys(eval_modules))
         first = {}
         for k, m in enumerate(eval_modules):
             first.setdefault(m, k)
         stats = accs[0].mode == "stats"
         crit = engine_criterion(self.criterion, self.device)  # None: the fused cross-entropy kernel
-        pipe = _BatchPipeline(eng) if stats and self._ckpt is None and crit is None else None
+        pipe = _BatchPipeline(eng) if stats and self._ckpt is None and crit is None and \
+            getattr(eng, "pipelined", True) else None
         # batches past the kernels' descriptor range run in slices (whole-batch loss scaling)
         big = (lambda x: eng.max_batch(tuple(x.shape[1:]))) if crit is None else None
         try:
@@ -634,7 +656,7 @@ class _AttributionMetric(ABC):
                 for i, x, y, lb in self._coalesced_batches(False, big):
                     def fold(res, dev=x.device):
                         slabs = [res[m] for m in uniq]
-                        sums = [accs[first[m]].ensure_sum(res[m].shape[-1], dev, m.num_features) for m in uniq]
+                        sums = [accs[first[m]].ensure_sum(res[m].shape[-1], dev, width(m)) for m in uniq]
                         for j in range(0, len(slabs), 16):
                             ops.score_fold_(slabs[j:j + 16], sums[j:j + 16], take_abs, 0)
 
@@ -647,14 +669,14 @@ class _AttributionMetric(ABC):
                         res = eng.grad_scores(x, y, set(uniq), mode, crit, loss_batch=lb, raw_slabs=stats)
                     if stats:
                         slabs = [res[m] for m in uniq]
-                        sums = [accs[first[m]].ensure_sum(res[m].shape[-1], x.device, m.num_features) for m in uniq]
+                        sums = [accs[first[m]].ensure_sum(res[m].shape[-1], x.device, width(m)) for m in uniq]
                         for j in range(0, len(slabs), 16):
                             ops.score_fold_(slabs[j:j + 16], sums[j:j + 16], take_abs, 0)
                         for m in uniq:
                             accs[first[m]].count += x.shape[0]
                     else:
                         for m in uniq:
-                            accs[first[m]].add(res[m][:, :m.num_features].contiguous(), i)
+                            accs[first[m]].add(res[m][:, :width(m)].contiguous(), i)
         finally:  # the tuner's in-flight concurrency is reset even if a batch raises
             if pipe is not None:
                 pipe.join()

@@ -30,7 +30,11 @@ class APoZAttributionMetric(_AttributionMetric):
             fused = self._fused_engine(eval_modules, why, need_ce=False, pre_act_ok=True)
             eng = None if fused is not None or not self._engines_allowed() else \
                 maybe_resnet_engine(self.model, eval_modules, self.device, why=why)
-            self._record_path("fused" if fused else "resnet" if eng else "generic", eval_modules, why)
+            mb = None
+            if fused is None and eng is None:
+                eng = mb = self._mobilenet_engine(eval_modules, why)  # opt-in; same forward-only pass
+            self._record_path("fused" if fused else "mobilenet" if mb else "resnet" if eng else "generic", eval_modules,
+                              why)
             if fused is not None:
                 accs = self._chain_pass(*fused, accs)
             elif eng is not None:
@@ -89,17 +93,20 @@ class APoZAttributionMetric(_AttributionMetric):
         return [accs[owner[b]] for b in blocks]
 
     def _engine_pass(self, eng, eval_modules, accs):
+        """ResNet engine (BN evaluation modules, two batches in flight) or MobileNet engine
+        (ReLU6 evaluation modules: ``eng.real_width``, one batch at a time)."""
         uniq = list(dict.fromkeys(eval_modules))
         stats = accs[0].mode == "stats"
         arena = None
-        pipe = _BatchPipeline(eng) if stats and self._ckpt is None else None
-        nf = sum(m.num_features for m in uniq)
+        pipe = _BatchPipeline(eng) if stats and self._ckpt is None and getattr(eng, "pipelined", True) else None
+        width = getattr(eng, "real_width", None) or (lambda m: m.num_features)
+        nf = sum(width(m) for m in uniq)
 
         def views(flat, B):
             bufs, off = {}, 0
             for m in uniq:
-                bufs[m] = flat[off:off + B * m.num_features].view(B, m.num_features)
-                off += B * m.num_features
+                bufs[m] = flat[off:off + B * width(m)].view(B, width(m))
+                off += B * width(m)
             return bufs
 
         try:
@@ -114,24 +121,24 @@ class APoZAttributionMetric(_AttributionMetric):
                         return bufs
 
                     def fold(bufs, dev=x.device):
-                        sums = [accs[k].ensure_sum(m.num_features, dev) for k, m in enumerate(eval_modules)]
+                        sums = [accs[k].ensure_sum(width(m), dev) for k, m in enumerate(eval_modules)]
                         ops.score_fold_([bufs[m] for m in eval_modules], sums, False, 0)
 
                     if pipe is not None and pipe.take(x, None, launch, fold):  # two batches in flight
                         for a in accs:
                             a.count += B
                         continue
-                    if arena is None or arena.shape[0] != B * sum(m.num_features for m in uniq) or not stats:
-                        arena = torch.zeros(B * sum(m.num_features for m in uniq), device=x.device)
+                    if arena is None or arena.shape[0] != B * sum(width(m) for m in uniq) or not stats:
+                        arena = torch.zeros(B * sum(width(m) for m in uniq), device=x.device)
                     else:
                         arena.zero_()
                     bufs, off = {}, 0
                     for m in uniq:
-                        bufs[m] = arena[off:off + B * m.num_features].view(B, m.num_features)
-                        off += B * m.num_features
+                        bufs[m] = arena[off:off + B * width(m)].view(B, width(m))
+                        off += B * width(m)
                     eng.forward(x, bufs)
                     if stats:  # one fold launch for every module's counts (fp64 column sums)
-                        sums = [accs[k].ensure_sum(m.num_features, x.device) for k, m in enumerate(eval_modules)]
+                        sums = [accs[k].ensure_sum(width(m), x.device) for k, m in enumerate(eval_modules)]
                         ops.score_fold_([bufs[m] for m in eval_modules], sums, False, 0)
                         for a in accs:
                             a.count += B

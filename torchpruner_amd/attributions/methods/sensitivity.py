@@ -22,10 +22,14 @@ class SensitivityAttributionMetric(_AttributionMetric):
             why = []
             fused = self._fused_engine(eval_modules, why, need_ce=False)  # any criterion (autograd on the logits)
             rn = None if fused is not None else self._resnet_grad_engine(eval_modules, why)
-            self._record_path("fused" if fused else "resnet" if rn else "generic", eval_modules, why)
+            mb = None
+            if fused is None and rn is None:
+                rn = mb = self._mobilenet_engine(eval_modules, why, grad=True)  # opt-in; same per-batch pass
+            self._record_path("fused" if fused else "mobilenet" if mb else "resnet" if rn else "generic", eval_modules,
+                              why)
             if fused is not None:  # VGG-style chains: |dL/da| partials from the fused dgrad epilogues
                 accs = self._fused_grad_pass(*fused, accs, "sensitivity", False)
-            elif rn is not None:  # ResNets: forward + input-grad backward on the HIP engine
+            elif rn is not None:  # ResNets, MobileNets: forward + input-grad backward on the HIP engine
                 accs = self._resnet_grad_pass(rn, eval_modules, accs, "sensitivity")
             else:
                 self._grad_capture_pass(eval_modules,

@@ -33,7 +33,11 @@ class TaylorAttributionMetric(_AttributionMetric):
         why = []
         fused = self._fused_engine(eval_modules, why, need_ce=False)  # any criterion (autograd on the logits)
         rn = None if fused is not None else self._resnet_grad_engine(eval_modules, why)
-        self._record_path("fused" if fused else "resnet" if rn else "generic", eval_modules, why)
+        if fused is None and rn is None:
+            rn = mb = self._mobilenet_engine(eval_modules, why, grad=True)  # opt-in; same per-batch pass
+        else:
+            mb = None
+        self._record_path("fused" if fused else "mobilenet" if mb else "resnet" if rn else "generic", eval_modules, why)
         if fused is not None:
             # native path: one fused forward + input-grad backward scores every module, then
             # ONE fold launch turns all layers' per-sample sums into |.| and fp64 accumulators

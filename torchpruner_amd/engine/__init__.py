@@ -5,10 +5,12 @@ from __future__ import annotations
 import torch
 
 from .fused_chain import FusedChainEngine, Plan, build_plan, criterion_is_cross_entropy, maybe_engine
+from .mobilenet_engine import MobileNetEngine, build_mobilenet_plan, maybe_mobilenet_engine
 from .resnet_engine import ResNetEngine, build_resnet_plan, maybe_resnet_engine
 
 __all__ = ["FusedChainEngine", "Plan", "build_plan", "criterion_is_cross_entropy", "maybe_engine", "ResNetEngine",
-           "build_resnet_plan", "maybe_resnet_engine", "native_logits", "invalidate"]
+           "build_resnet_plan", "maybe_resnet_engine", "MobileNetEngine", "build_mobilenet_plan",
+           "maybe_mobilenet_engine", "native_logits", "invalidate"]
 
 
 def invalidate(model) -> bool:
@@ -18,9 +20,9 @@ def invalidate(model) -> bool:
     in-place edits through ``param.data`` bypass the version counter, so call this after them.
     Also marks every cached training-conv weight pack stale (:func:`.train.invalidate_packs`).
     Returns True when something was cached."""
-    from . import fused_chain, resnet_engine, train
+    from . import fused_chain, mobilenet_engine, resnet_engine, train
     hit = train.invalidate_packs() > 0
-    for cache in (fused_chain._ENGINES, resnet_engine._ENGINES):
+    for cache in (fused_chain._ENGINES, resnet_engine._ENGINES, mobilenet_engine._ENGINES):
         if model in cache:
             if torch.cuda.is_available() and torch.cuda.is_initialized():
                 # replays of the engine's captured graphs may still run on pipeline streams, and

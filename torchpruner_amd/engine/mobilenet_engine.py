@@ -1,0 +1,410 @@
+"""Attribution engine for MobileNetV2-style nets (torchvision layout: conv3x3-BN-ReLU6 stem,
+inverted-residual blocks, conv1x1-BN-ReLU6 head, global average pool, classifier) on the HIP kernels.
+
+The hidden (expanded) activation of a block is the largest tensor of the net; on the generic path an
+eval-mode block passes over it eleven times in the forward alone (conv write, BN, ReLU6, depthwise,
+BN, ReLU6, each read + write). Here:
+
+  stem     NCHW -> NHWC pad to 4 channels, 3x3 implicit GEMM (``tpamd.conv_gen``) with the eval BN
+           folded into the epilogue affine; the PRE-activation z is stored (``relu=False``)
+  expand   1x1 ``conv_gen``, BN folded, ``relu=False``: stores z. Its APoZ epilogue counts z > 0,
+           which is the ReLU6 output's positive count
+  dw       ``tpamd.dwconv_act_fwd``: clamps z to [0, 6] as it loads it, BN folded, ReLU6 on the way
+           out, APoZ counts of the output (csrc/kernels/dwconv_act.hip)
+  project  1x1 ``conv_gen``, BN folded, linear (its true form), the shortcut as ``res=``
+  head     1x1 ``conv_gen`` storing z, then clamp + global average pool + classifier GEMM (two
+           elementwise passes over the smallest activation)
+
+ReLU6 never touches the GEMM kernels. The backward runs block by block, last block first: the
+project dgrad (``conv_gen_bwd``, BN scale folded into the operand, no mask), the post-depthwise
+score as a channel reduction of (y, g), ``tpamd.dwconv_act_dgrad`` (masks g by the stored y, gathers,
+reduces the post-expand ReLU6's Taylor / Sensitivity partials from the unmasked gradient, masks by
+z), and the expand dgrad with the block's output gradient as ``res=`` when there is a shortcut.
+
+Channels are carried zero-padded to a multiple of 32 (``cpad``) as in the ResNet engine, whose conv
+plumbing (packing, tuner, classifier GEMMs, partial-slab arena) this engine inherits. One batch at a
+time: no two-stream pipeline, no graph replay. fp32 throughout.
+"""
+from __future__ import annotations
+
+import weakref
+from dataclasses import dataclass, field
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+from .fused_chain import cpad, logits_grad
+from .resnet_engine import ResNetEngine, _Conv
+
+_RELU6, _TAY_MODES = 2, {"taylor": 0, "taylor_signed": 0, "sensitivity": 1}
+
+
+@dataclass
+class _Unit:
+    """conv -> BN -> ReLU6"""
+    conv: nn.Conv2d
+    bn: nn.BatchNorm2d
+    act: nn.Module
+
+
+@dataclass
+class _IRBlock:
+    expand: Optional[_Unit]
+    dw: _Unit
+    project: _Conv
+    shortcut: bool
+
+
+@dataclass
+class MobileNetPlan:
+    stem: _Unit
+    head: _Unit
+    fc: nn.Linear
+    blocks: list = field(default_factory=list)
+
+
+def _conv_kind(conv) -> str:
+    """"dense", "depthwise", or the reason the engine cannot run the conv; read from the weight's
+    shape (pruning leaves ``in_channels`` / ``out_channels`` stale)."""
+    if not isinstance(conv, nn.Conv2d):
+        return f"expected a Conv2d, found {type(conv).__name__}"
+    if conv.dilation not in (1, (1, 1)):
+        return f"dilation {tuple(conv.dilation)} is not supported"
+    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        return "only explicit zero padding is supported"
+    k = conv.weight.shape[2:]
+    if k[0] != k[1] or conv.stride[0] != conv.stride[1] or conv.padding[0] != conv.padding[1]:
+        return "only square kernels, strides and paddings are supported"
+    if conv.groups == 1:
+        return "dense"
+    cout, cin_g = conv.weight.shape[:2]
+    if cin_g != 1:
+        return f"grouped conv (groups {conv.groups}, {cin_g} inputs per group) is not supported"
+    if cout != conv.groups:
+        return f"depth multiplier {cout / conv.groups:g} is not supported (only 1)"
+    return "depthwise"
+
+
+def _unit(seq, what):
+    """(_Unit, "") of a conv-BN-ReLU6 Sequential, else (None, reason)."""
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        return None, f"{what}: expected a (conv, BN, ReLU6) Sequential"
+    conv, bn, act = seq
+    kind = _conv_kind(conv)
+    if kind not in ("dense", "depthwise"):
+        return None, f"{what}: {kind}"
+    if not isinstance(bn, nn.BatchNorm2d) or bn.running_mean is None:
+        return None, f"{what}: expected a BatchNorm2d with running statistics after the conv"
+    if not isinstance(act, nn.ReLU6):
+        return None, f"{what}: activation {type(act).__name__} is not supported (only ReLU6)"
+    return _Unit(conv, bn, act), ""
+
+
+def _is_1x1(conv) -> bool:
+    return tuple(conv.weight.shape[2:]) == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+
+
+def build_mobilenet_plan(model: nn.Module):
+    """Lower a torchvision-layout MobileNetV2, or return (None, reason)."""
+    feats, cls = getattr(model, "features", None), getattr(model, "classifier", None)
+    if not isinstance(feats, nn.Sequential) or len(feats) < 3 or cls is None or \
+            not any(isinstance(getattr(m, "conv", None), nn.Sequential) for m in feats):
+        return None, "not a torchvision-layout MobileNetV2 (features / inverted-residual blocks / classifier)"
+    pool = getattr(model, "avgpool", None)
+    if pool is not None and not (isinstance(pool, nn.AdaptiveAvgPool2d) and pool.output_size in (1, (1, 1))):
+        return None, "unsupported pool before the classifier (needs a global AdaptiveAvgPool2d)"
+    layers = list(cls.children()) if isinstance(cls, nn.Sequential) else [cls]
+    if not layers or not isinstance(layers[-1], nn.Linear) or not all(isinstance(m, nn.Dropout) for m in layers[:-1]):
+        return None, "unsupported classifier (needs Dropout layers and a final Linear)"
+    stem, why = _unit(feats[0], "stem")
+    if stem is None:
+        return None, why
+    if _conv_kind(stem.conv) != "dense" or stem.conv.weight.shape[2] != 3 or stem.conv.weight.shape[1] > 4 or \
+            stem.conv.padding[0] != 1:
+        return None, "unsupported stem (needs a 3x3 conv, padding 1, of at most 4 input channels)"
+    head, why = _unit(feats[-1], "head")
+    if head is None:
+        return None, why
+    if _conv_kind(head.conv) != "dense" or not _is_1x1(head.conv):
+        return None, "unsupported head (needs a 1x1 conv)"
+    plan = MobileNetPlan(stem, head, layers[-1])
+    width = stem.conv.weight.shape[0]
+    for i, blk in enumerate(feats[1:-1], 1):
+        seq = getattr(blk, "conv", None)
+        what = f"features.{i}"
+        if not isinstance(seq, nn.Sequential) or len(seq) not in (3, 4):
+            return None, f"{what}: expected an inverted-residual block ([1x1-BN-ReLU6,] depthwise-BN-ReLU6, 1x1, BN)"
+        expand = None
+        if len(seq) == 4:
+            expand, why = _unit(seq[0], f"{what} expand")
+            if expand is None:
+                return None, why
+            if _conv_kind(expand.conv) != "dense" or not _is_1x1(expand.conv):
+                return None, f"{what}: the expand conv must be a dense 1x1 conv"
+        dw, why = _unit(seq[-3], f"{what} depthwise")
+        if dw is None:
+            return None, why
+        k, s, pd = dw.conv.weight.shape[2], dw.conv.stride[0], dw.conv.padding[0]
+        if _conv_kind(dw.conv) != "depthwise" or k not in (3, 5) or s not in (1, 2) or pd > k - 1:
+            return None, f"{what}: the depthwise conv must be 3x3 / 5x5, stride 1 / 2, padding < k, depth multiplier 1"
+        proj, bn = seq[-2], seq[-1]
+        kind = _conv_kind(proj)
+        if kind != "dense" or not _is_1x1(proj):
+            return None, f"{what}: the project conv must be a dense 1x1 conv" + ("" if kind == "dense" else f" ({kind})")
+        if not isinstance(bn, nn.BatchNorm2d) or bn.running_mean is None:
+            return None, f"{what}: expected a BatchNorm2d with running statistics after the project conv"
+        hidden = dw.conv.weight.shape[0]
+        if (expand.conv.weight.shape[:2] if expand else (hidden, width)) != (hidden, width) or \
+                proj.weight.shape[1] != hidden:
+            return None, f"{what}: channel counts of the block's convs do not chain"
+        cout = proj.weight.shape[0]
+        shortcut = getattr(blk, "use_res_connect", None)
+        if shortcut is None:
+            shortcut = s == 1 and cout == width
+        if shortcut and (s != 1 or cout != width):
+            return None, f"{what}: a shortcut needs stride 1 and equal widths"
+        plan.blocks.append(_IRBlock(expand, dw, _Conv(proj, bn), bool(shortcut)))
+        width = cout
+    if head.conv.weight.shape[1] != width or plan.fc.weight.shape[1] != head.conv.weight.shape[0]:
+        return None, "channel counts of the head / classifier do not chain"
+    return plan, ""
+
+
+def _out_hw(conv, H, W):
+    k, s, pd = conv.weight.shape[2], conv.stride[0], conv.padding[0]
+    return (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
+
+
+class MobileNetEngine(ResNetEngine):
+    pipelined = False  # attributions/base.py: one batch at a time (no _BatchPipeline)
+
+    def __init__(self, model: nn.Module, plan: MobileNetPlan):
+        super().__init__(model, plan)
+
+    # ------------------------------------------------------------------ structure
+    def _all_convs(self):
+        p = self.plan
+        out = [p.stem]
+        for b in p.blocks:
+            out += ([b.expand] if b.expand is not None else []) + [b.dw, b.project]
+        return out + [p.head]
+
+    def eval_modules(self):
+        """The ReLU6 modules the engine scores: per block the post-expand one (where the block
+        expands) and the post-depthwise one."""
+        mods = []
+        for b in self.plan.blocks:
+            mods += ([b.expand.act] if b.expand is not None else []) + [b.dw.act]
+        return mods
+
+    def real_width(self, module) -> int:
+        """Channels of an evaluation module's output (the engine's slabs are padded past it)."""
+        for b in self.plan.blocks:
+            if module is b.dw.act or (b.expand is not None and module is b.expand.act):
+                return b.dw.conv.weight.shape[0]
+        raise KeyError("not a block ReLU6 of this MobileNet")
+
+    def _stem_fused(self) -> bool:
+        """The first block's depthwise conv reads the stem's pre-activation and clamps it itself
+        (no expand conv and no shortcut need the activated stem output)."""
+        b0 = self.plan.blocks[0]
+        return b0.expand is None and not b0.shortcut
+
+    def max_batch(self, sample_shape) -> int:
+        H, W = tuple(sample_shape)[-2:]
+        per = 4 * H * W * 4  # the channel-padded NHWC input
+        H, W = _out_hw(self.plan.stem.conv, H, W)
+        per = max(per, 4 * H * W * cpad(self.plan.stem.conv.weight.shape[0]))
+        for b in self.plan.blocks:
+            hid = cpad(b.dw.conv.weight.shape[0])
+            # the hidden activation, and the partial slab of its gradient kernel beside it
+            per = max(per, 4 * H * W * hid, 4 * ops.dwconv_act_tay_slots(H, W, hid) * hid)
+            H, W = _out_hw(b.dw.conv, H, W)
+            per = max(per, 4 * H * W * hid, 4 * H * W * cpad(b.project.conv.weight.shape[0]))
+        per = max(per, 4 * H * W * cpad(self.plan.head.conv.weight.shape[0]))
+        return max(1, ((1 << 31) - 1) // per)
+
+    # ------------------------------------------------------------------ packing
+    @torch.no_grad()
+    def _pack_dw(self, u: _Unit):
+        from .resnet_engine import _fold
+        w = u.conv.weight.detach().float()
+        c = w.shape[0]
+        cp = cpad(c)
+        scale, shift = _fold(u.conv, u.bn)
+        # padded channels: zero weights and a zero affine -> exact zeros in y, dz and the scores
+        return {"w": F.pad(w, (0, 0, 0, 0, 0, 0, 0, cp - c)).contiguous(), "scale": F.pad(scale, (0, cp - c)),
+                "shift": F.pad(shift, (0, cp - c)), "stride": u.conv.stride[0], "pad": u.conv.padding[0]}
+
+    def _pack(self):
+        key = self._params_key()
+        if key == self._key:
+            return self._packed
+        p = self.plan
+        blocks = []
+        for b in p.blocks:
+            blocks.append({"expand": self._pack_conv(b.expand) if b.expand is not None else None,
+                           "dw": self._pack_dw(b.dw), "project": self._pack_conv(b.project)})
+        fc_w = p.fc.weight.detach().float()
+        fc_w = F.pad(fc_w, (0, cpad(fc_w.shape[1]) - fc_w.shape[1]))
+        fc_b = p.fc.bias.detach().float() if p.fc.bias is not None else torch.zeros(fc_w.shape[0], device=fc_w.device)
+        n_cls = fc_w.shape[0]
+        fc_wt = F.pad(fc_w, (0, 0, 0, cpad(n_cls) - n_cls)).t().contiguous()
+        self._packed = {"stem": self._pack_conv(p.stem, stem=True), "blocks": blocks, "head": self._pack_conv(p.head),
+                        "fc_w": fc_w.contiguous(), "fc_b": fc_b.contiguous(), "fc_wt": fc_wt}
+        self._key = key
+        return self._packed
+
+    # ------------------------------------------------------------------ forward
+    def _block(self, T, blk, e, h, in_act, apoz=None, saved=None):
+        """One inverted-residual block from its (linear, or for a fused stem pre-activation) input
+        ``h``; appends (input, z, y, input activation code) to ``saved``."""
+        apoz = apoz or {}
+        if blk.expand is not None:
+            z = self._conv(T, e["expand"], h, False, apoz=apoz.get(blk.expand.act))
+            in_act = _RELU6
+        else:
+            z = h
+        d = e["dw"]
+        y = T.dwconv_act_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, _RELU6,
+                             apoz.get(blk.dw.act))
+        out = self._conv(T, e["project"], y, False, res=h if blk.shortcut else None)
+        if saved is not None:
+            saved.append((h, z, y, in_act))
+        return out
+
+    def forward(self, x: torch.Tensor, apoz: Optional[dict] = None, save: bool = False):
+        """Logits of the network; ``apoz`` maps evaluation modules (:meth:`eval_modules`) to zeroed
+        (B, C) float tensors that receive the per-sample counts of positive outputs.
+        ``save=True`` returns (logits, saved) for :meth:`grad_scores`."""
+        T = ops.require()
+        P = self._pack()
+        apoz = dict(apoz or {})
+        padded = []  # (user buffer, padded scratch) for channel counts that are not multiples of 32
+        for m, buf in apoz.items():
+            if buf.shape[1] % 32:
+                tmp = buf.new_zeros(buf.shape[0], cpad(buf.shape[1]))
+                padded.append((buf, tmp))
+                apoz[m] = tmp
+        h = T.nchw_to_nhwc_pad(x.float().contiguous(), 4)
+        h = self._conv(T, P["stem"], h, False)  # the stem's pre-activation
+        in_act = _RELU6
+        if not self._stem_fused():
+            h, in_act = h.clamp_(0.0, 6.0), 0
+        saved = []
+        for blk, e in zip(self.plan.blocks, P["blocks"]):
+            h = self._block(T, blk, e, h, in_act, apoz, saved if save else None)
+            in_act = 0
+        zh = self._conv(T, P["head"], h, False)
+        feat = T.avgpool_nhwc(zh.clamp(0.0, 6.0))
+        for buf, tmp in padded:
+            buf.add_(tmp[:, :buf.shape[1]])
+        logits = self._fc(T, P, feat)
+        if save:
+            saved.append((zh, feat))
+            return logits, saved
+        return logits
+
+    # ------------------------------------------------------------------ backward (Taylor, Sensitivity)
+    def grad_scores(self, x: torch.Tensor, y: torch.Tensor, want, mode: str, criterion=None,
+                    loss_batch: Optional[int] = None, raw_slabs: bool = False):
+        """One engine forward + input-gradient-only backward of the loss; returns
+        {ReLU6 module: (B, C_padded) per-sample ``ops.channel_reduce`` score} for the modules of
+        :meth:`eval_modules` in ``want``. No weight gradients, no autograd graph; the backward stops
+        at the earliest block holding a wanted module. ``raw_slabs``: a score that came from the
+        depthwise gradient kernel's epilogue stays its raw (R, B, C_padded) partial-slot slab for
+        ``ops.score_fold_`` to finish (slot sum, and |.| for "taylor")."""
+        T = ops.require()
+        P = self._pack()
+        logits, saved = self.forward(x, save=True)
+        zh, feat = saved.pop()
+        B = logits.shape[0]
+        blocks = self.plan.blocks
+        first = min((bi for bi, b in enumerate(blocks)
+                     if b.dw.act in want or (b.expand is not None and b.expand.act in want)), default=None)
+        out = {}
+        if first is None:
+            return out
+        g_log = logits_grad(logits, y, criterion, loss_batch)
+        g_feat = self._fc_bwd(T, P, g_log, feat)  # (B, C_head padded)
+        HW = zh.shape[1] * zh.shape[2]
+        # avg-pool backward + the head's ReLU6 (zero gradient at exactly 0 and 6)
+        g = torch.where((zh > 0) & (zh < 6), (g_feat / HW)[:, None, None, :], torch.zeros((), device=x.device))
+        g, _ = self._dgrad(T, P["head"], g.contiguous(), None)  # dL/d(last block's output)
+        akey = (tuple(x.shape), mode, tuple(sorted(i for i, m in enumerate(self.eval_modules()) if m in want)))
+        size = self._arena_sizes.get(akey)
+        arena = [torch.zeros(size, device=x.device) if size else None, 0, 0]
+        for bi in range(len(blocks) - 1, first - 1, -1):
+            blk, e = blocks[bi], P["blocks"][bi]
+            h, z, yd, in_act = saved[bi]
+            gy, _ = self._dgrad(T, e["project"], g, None)  # dL/d(depthwise ReLU6 output), unmasked
+            if blk.dw.act in want:
+                out[blk.dw.act] = ops.channel_reduce(yd.permute(0, 3, 1, 2), gy.permute(0, 3, 1, 2), mode)
+            ex_wanted = blk.expand is not None and blk.expand.act in want
+            if bi == first and not ex_wanted:
+                break
+            d = e["dw"]
+            _, H, W, C = z.shape
+            tay = self._slab(arena, T.dwconv_act_tay_slots(H, W, C), B, C, x.device) if ex_wanted else None
+            dz = T.dwconv_act_dgrad(gy, yd, d["w"], d["scale"], z, H, W, d["stride"], d["pad"], in_act, _RELU6, tay,
+                                    _TAY_MODES[mode])
+            if ex_wanted:
+                if raw_slabs:
+                    out[blk.expand.act] = tay
+                else:
+                    sums = tay.sum(0)
+                    out[blk.expand.act] = sums.abs_() if mode == "taylor" else sums
+            if bi == first:
+                break
+            if blk.expand is not None:  # the block input is linear: no mask
+                g, _ = self._dgrad(T, e["expand"], dz, None, res=g if blk.shortcut else None)
+            else:
+                g = dz + g if blk.shortcut else dz
+        if arena[2] > (size or 0):
+            self._arena_sizes[akey] = arena[2]
+        return out
+
+    # ------------------------------------------------------------------ not served
+    def locate(self, bn):
+        raise NotImplementedError("Shapley does not run on the MobileNet engine")
+
+    forward_to = logits_from = locate
+
+
+_ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
+
+
+def mobilenet_engine_default() -> bool:
+    """``TORCHPRUNER_MOBILENET_ENGINE`` (default 0: the engine is opt-in)."""
+    import os
+    return os.environ.get("TORCHPRUNER_MOBILENET_ENGINE", "0") not in ("0", "")
+
+
+def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None):
+    """A MobileNetEngine when every eval module is a block ReLU6 the engine serves, else None
+    (``why`` receives the reason). ``grad`` is accepted for symmetry with the ResNet engine: the
+    same modules are served forward (APoZ) and backward (Taylor, Sensitivity)."""
+    from .fused_chain import _reject, engines_enabled
+    dev = torch.device(device) if not isinstance(device, torch.device) else device
+    if not engines_enabled():
+        return _reject(why, "mobilenet engine: engines disabled (TORCHPRUNER_ENGINES=0)")
+    if dev.type != "cuda" or ops.backend() == "torch" or not ops.available() or model.training:
+        return _reject(why, "mobilenet engine: needs an eval-mode model on a GPU with the native extension")
+    if any(p.dtype != torch.float32 for p in model.parameters()):
+        return _reject(why, "mobilenet engine: parameters are not float32")
+    plan, reason = build_mobilenet_plan(model)  # re-validated every run: pruning changes channel counts
+    if plan is None:
+        return _reject(why, f"mobilenet engine: {reason}")
+    eng = _ENGINES.get(model)
+    if eng is None or [c.conv for c in eng._all_convs()] != [c.conv for c in MobileNetEngine(model, plan)._all_convs()] \
+            or [b.shortcut for b in eng.plan.blocks] != [b.shortcut for b in plan.blocks]:
+        eng = MobileNetEngine(model, plan)
+        _ENGINES[model] = eng
+    ok = set(map(id, eng.eval_modules()))
+    if not all(id(m) in ok for m in eval_modules):
+        return _reject(why, "mobilenet engine: evaluation modules must be the ReLU6 after a block's expand or "
+                            "depthwise conv (use find_best_evaluation_module=True)")
+    return eng

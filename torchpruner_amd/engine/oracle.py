@@ -15,6 +15,9 @@ attributions.py:58-68); ``decision_flips`` counts where the two runs' decisions 
 
 Runs on the CPU in fp64 on one batch (the per-batch mean loss of the reference,
 attributions.py:66): the caller loops batches and reduces.
+
+``mobilenet_scores_fp64`` is the same idea for the MobileNet engine, with ReLU6's three-way
+decision (<= 0 / in between / >= 6) replayed through an autograd pass of a float64 copy of the model.
 """
 from __future__ import annotations
 
@@ -169,3 +172,90 @@ def engine_scores_fp64(engine, x, y, conditioned=True, mode="taylor", totals=Non
         g_out = torch.nn.grad.conv2d_input(prev.shape, plan.convs[ci].conv.weight.detach().double().cpu(), g_pre,
                                            padding=1)
     return scores, flips
+
+
+def mobilenet_scores_fp64(engine, model, x, y, mode="taylor", conditioned=True, criterion=None):
+    """fp64 oracle of the MobileNet engine's scores on one batch: a CPU autograd pass of a float64
+    copy of ``model`` (every ReLU6 out of place), scored at the ReLU6 modules the engine serves
+    (``MobileNetEngine.eval_modules``: post-expand and post-depthwise of every block).
+
+    ``conditioned=True`` replays the engine's own three-way decision of EVERY ReLU6 of the net
+    (<= 0 / in between / >= 6, read from the pre-activations and clamped outputs its fp32 forward
+    saved) in the fp64 pass: the output is the fp64 pre-activation where the engine passed it, else
+    the constant 0 or 6, and the gradient flows exactly where the engine let it. The engine's
+    scores must then match to fp32 rounding of the arithmetic alone. ``conditioned=False`` is the
+    plain fp64 run (``engine`` may be None: nothing is replayed or counted).
+
+    Returns (scores, flips, totals): ``scores[module]`` (keyed by the modules of ``model``) is the
+    (B, C) fp64 per-sample score as ``ops.channel_reduce`` defines ``mode`` ("taylor",
+    "taylor_signed", "sensitivity") for the batch-mean loss (cross-entropy, or ``criterion``);
+    ``flips[name]`` / ``totals[name]`` count, per ReLU6, the units whose decision differs between
+    the engine and fp64 given the same upstream decisions, and the units, for
+    :func:`flip_violations`."""
+    import copy
+
+    import torch.nn as nn
+    assert engine is not None or not conditioned, "replaying decisions needs the engine"
+    m64 = copy.deepcopy(model).double().cpu().eval()
+    names = {id(m): n for n, m in m64.named_modules()}
+    relus = [m for m in m64.modules() if isinstance(m, nn.ReLU6)]
+    for m in relus:
+        m.inplace = False
+    orig = [m for m in model.modules() if isinstance(m, nn.ReLU6)]
+    decided = {}  # ReLU6 of the copy -> engine tensor holding its decision (NHWC, padded width)
+    if engine is not None:
+        with torch.no_grad():
+            saved = engine.forward(x, save=True)[1]
+        zh, _ = saved[-1]
+        eng_mods = {id(o): c for o, c in zip(orig, relus)}
+        plan = engine.plan
+        decided[eng_mods[id(plan.stem.act)]] = saved[0][0]  # pre-activation, or the clamped output: same regions
+        decided[eng_mods[id(plan.head.act)]] = zh
+        for blk, (_, z, yd, _) in zip(plan.blocks, saved[:-1]):
+            if blk.expand is not None:
+                decided[eng_mods[id(blk.expand.act)]] = z
+            decided[eng_mods[id(blk.dw.act)]] = yd
+    flips, totals, outs = {}, {}, {}
+
+    def hook(mod, inp, out):
+        z = inp[0]
+        t = decided.get(mod)
+        if t is not None:
+            tf = _nchw(t, z.shape[1])
+            lo_f, hi_f = tf <= 0, tf >= 6
+            flips[names[id(mod)]] = int(((lo_f != (z <= 0)) | (hi_f != (z >= 6))).sum())
+            totals[names[id(mod)]] = z.numel()
+            if conditioned:
+                const = torch.where(hi_f, torch.full((), 6.0, dtype=z.dtype), torch.zeros((), dtype=z.dtype))
+                out = torch.where(lo_f | hi_f, const, z)
+        outs[mod] = out
+        if out.requires_grad:
+            out.retain_grad()
+        return out
+
+    handles = [m.register_forward_hook(hook) for m in relus]
+    try:
+        with torch.enable_grad():
+            xin = x.detach().double().cpu().requires_grad_(True)  # keeps every activation in the graph
+            logits = m64(xin)
+            loss = F.cross_entropy(logits, y.cpu()) if criterion is None else criterion(logits, y.cpu())
+            loss.backward()
+    finally:
+        for h in handles:
+            h.remove()
+    if engine is not None:
+        served = [eng_mods[id(m)] for m in engine.eval_modules()], engine.eval_modules()
+    else:
+        from .mobilenet_engine import build_mobilenet_plan
+        plan, why = build_mobilenet_plan(model)
+        assert plan is not None, why
+        p64 = build_mobilenet_plan(m64)[0]
+        pick = lambda p: [a for b in p.blocks for a in (([b.expand.act] if b.expand is not None else []) + [b.dw.act])]
+        served = pick(p64), pick(plan)
+    scores = {}
+    for c, o in zip(*served):
+        a, g = outs[c].detach(), outs[c].grad
+        v = g.abs() if mode == "sensitivity" else -(g * a)
+        v = v.flatten(2).sum(-1)
+        scores[o] = v.abs() if mode == "taylor" else v
+    return scores, flips, totals

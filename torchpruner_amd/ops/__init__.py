@@ -11,11 +11,13 @@ from typing import Sequence
 import torch
 
 from ._native import available, backend, load, require, use_native
+from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 
 __all__ = [
     "available", "backend", "load", "require", "use_native",
     "REDUCE_MODES", "channel_reduce", "column_accumulate", "score_fold_", "channel_fill_", "nan_channels",
     "gather_multi", "prefix_mask", "shapley_scatter", "shapley_column", "cross_entropy",
+    "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
 ]
 
 REDUCE_MODES = {"taylor": 0, "taylor_signed": 1, "sensitivity": 2, "apoz": 3, "sum_grad": 4}
