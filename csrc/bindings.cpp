@@ -214,6 +214,39 @@ at::Tensor prefix_mask(const at::Tensor& z, const at::Tensor& rank, int64_t p0, 
   return out;
 }
 
+// out[0] = base, out[j] = out[j-1] - (a[:, c] - fill[c]) (x) wt[c, :], c = perm[p0 + j - 1]: the cnt stacked outputs
+// of a 1x1 project conv whose input copies differ by one filled channel each (csrc/kernels/prefix_project.hip)
+at::Tensor prefix_project(const at::Tensor& base, const at::Tensor& a, const at::Tensor& fill, const at::Tensor& wt,
+                          const at::Tensor& perm, int64_t p0, int64_t cnt) {
+  check_cuda_f32(base, "base");
+  check_cuda_f32(a, "a");
+  check_cuda_f32(fill, "fill");
+  check_cuda_f32(wt, "wt");
+  TORCH_CHECK(base.dim() == 2 && base.is_contiguous() && base.numel() > 0, "base must be a non-empty contiguous (N, Co)");
+  const int64_t N = base.size(0), Co = base.size(1);
+  TORCH_CHECK(a.dim() == 2 && a.is_contiguous() && a.size(0) == N && a.size(1) > 0, "a must be a contiguous (N, C)");
+  const int64_t C = a.size(1);
+  TORCH_CHECK(fill.dim() == 1 && fill.is_contiguous() && fill.numel() == C, "fill must be a contiguous (C,)");
+  TORCH_CHECK(wt.dim() == 2 && wt.is_contiguous() && wt.size(0) == C && wt.size(1) == Co,
+              "wt must be a contiguous (C, Co)");
+  TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_cuda() && perm.dim() == 1 && perm.is_contiguous(),
+              "perm must be a contiguous int32 (n,) GPU tensor");
+  TORCH_CHECK(a.device() == base.device() && fill.device() == base.device() && wt.device() == base.device() &&
+                  perm.device() == base.device(), "operands must share a device");
+  const int64_t n = perm.numel(), lim = int64_t(1) << 31;
+  TORCH_CHECK(Co % 4 == 0, "prefix_project needs Co % 4 == 0");
+  TORCH_CHECK(n <= C && cnt >= 1 && p0 >= 0 && p0 + cnt - 1 <= n, "bad prefix range (p0 ", p0, ", cnt ", cnt, ", n ", n,
+              ", C ", C, ")");
+  TORCH_CHECK(N < lim && C < lim && Co < lim && cnt < lim && N * Co * 4 < lim && N * Co * 4 * cnt < lim,
+              "prefix_project operands must stay below 2^31 bytes");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(base.device());
+  auto out = at::empty({cnt, N, Co}, base.options());
+  TP_CHECK_HIP(tp_prefix_project(base.data_ptr<float>(), a.data_ptr<float>(), fill.data_ptr<float>(),
+                                 wt.data_ptr<float>(), perm.data_ptr<int>(), out.data_ptr<float>(), (int)N, (int)C,
+                                 (int)Co, (int)n, (int)p0, (int)cnt, cur_stream()));
+  return out;
+}
+
 void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv, int64_t row0, int64_t k0,
                      double scale) {
   check_cuda_f32(L, "losses");
@@ -536,6 +569,7 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("nan_channels(Tensor x) -> Tensor");
   m.def("gather_multi(Tensor[] srcs, int[] axes, Tensor keep) -> Tensor[]");
   m.def("prefix_mask(Tensor z, Tensor rank, int p0, int K) -> Tensor");
+  m.def("prefix_project(Tensor base, Tensor a, Tensor fill, Tensor wt, Tensor perm, int p0, int cnt) -> Tensor");
   m.def("shapley_scatter(Tensor L, Tensor perm, Tensor(a!) sv, int row0, int k0, float scale) -> ()");
   m.def("shapley_column(Tensor L, Tensor perm, Tensor(a!) sv_col, int k0, float scale) -> ()");
   m.def("cross_entropy(Tensor logits, Tensor target, float gscale, bool want_grad) -> (Tensor, Tensor)");
@@ -563,6 +597,7 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("nan_channels", &nan_channels);
   m.impl("gather_multi", &gather_multi);
   m.impl("prefix_mask", &prefix_mask);
+  m.impl("prefix_project", &prefix_project);
   m.impl("shapley_scatter", &shapley_scatter);
   m.impl("shapley_column", &shapley_column);
   m.impl("cross_entropy", &cross_entropy);

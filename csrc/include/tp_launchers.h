@@ -25,6 +25,10 @@ hipError_t tp_shapley_column(const float* L, const int* perm, double* sv_col, in
                              hipStream_t st);
 hipError_t tp_cross_entropy(const float* logits, const int64_t* target, float* loss, float* grad, int B, int NC,
                             float gscale, hipStream_t st);
+// prefix_project.hip: out[0] = base, out[j] = out[j-1] - (a[:, c] - fill[c]) (x) wt[c, :], c = perm[p0+j-1]
+// (base (N, Co), a (N, C), fill (C), wt (C, Co), perm (n <= C), out (cnt, N, Co); Co % 4 == 0)
+hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt, const int* perm,
+                             float* out, int N, int C, int Co, int n, int p0, int cnt, hipStream_t st);
 // train_ops.hip
 hipError_t tp_dropout(const float* x, float* y, long long n, unsigned long long seed, double p, hipStream_t st);
 hipError_t tp_maxpool_fwd_arg(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, int k, int s, int pad,

@@ -159,7 +159,7 @@ class _AttributionMetric(ABC):
             "compute_dtype must be None, torch.float32, torch.bfloat16 or torch.float16"
         self.compute_dtype = compute_dtype
         # MobileNet engine (engine/mobilenet_engine.py): opt-in. None reads TORCHPRUNER_MOBILENET_ENGINE
-        # (default 0); APoZ / Taylor / Sensitivity then try fused -> resnet -> mobilenet -> generic
+        # (default 0); APoZ / Taylor / Sensitivity / Shapley then try fused -> resnet -> mobilenet -> generic
         self.mobilenet_engine = mobilenet_engine
         self._ckpt = None
         self._run_accs = None

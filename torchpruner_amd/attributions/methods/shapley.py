@@ -77,6 +77,9 @@ class ShapleyAttributionMetric(_AttributionMetric):
         if fused is None:
             fused = self._resnet_prepare(module, why)
             path = "resnet" if fused is not None else None
+        if fused is None:
+            fused = self._mobilenet_prepare(module, why)
+            path = "mobilenet" if fused is not None else None
         if fused is not None:
             self._record_path(path, [module], why)
             return self._run_batches(module, sv_samples, fused)
@@ -298,15 +301,7 @@ class ShapleyAttributionMetric(_AttributionMetric):
         n = engine.real_width(k)
         pad_rank = _RankPadder(n)
         delta = engine.prefix_delta_ok(k)
-        perms = {}
-
-        def perm_of(rank_t):  # permutation from its rank vector (cached per rank vector)
-            hit = perms.get(id(rank_t))
-            if hit is None or hit[0] is not rank_t:
-                p = torch.empty_like(rank_t)
-                p[rank_t.long()] = torch.arange(rank_t.numel(), dtype=rank_t.dtype, device=rank_t.device)
-                hit = perms[id(rank_t)] = (rank_t, p)
-            return hit[1]
+        perm_of = _PermOf()
 
         def prepare(x, y):
             zk, _ = engine.forward(x, stop_after=k)  # engine layout (B, H, W, C padded)
@@ -358,6 +353,37 @@ class ShapleyAttributionMetric(_AttributionMetric):
                 return loss.view(cnt, B)
 
             return n, B, 2 * a[0].numel(), base, evaluate
+
+        return prepare
+
+    def _mobilenet_prepare(self, module, why=None):
+        """Prefix evaluation on the MobileNet engine (opt-in; the ReLU6 after a block's expand or
+        depthwise conv, any loss): the block's input and post-depthwise output are produced once per
+        batch; the K stacked outputs of the block's linear project conv come from one conv of the
+        base prefix and a running rank-1 subtraction per pixel (``ops.prefix_project``; the K masked
+        copies of the 6x wider hidden activation are never built), and go through the rest of the
+        network in ONE engine forward."""
+        from ...engine.fused_chain import engine_criterion, per_sample_loss
+        eng = self._mobilenet_engine([module], why)
+        if eng is None:
+            return None
+        crit = engine_criterion(self.criterion, self.device)  # None: the fused cross-entropy kernel
+        bi, kind = eng.locate(module)
+        n = eng.real_width(module)
+        pad_rank, perm_of = _RankPadder(n), _PermOf()
+
+        def prepare(x, y):
+            h, yd = eng.forward_to(x, bi)
+            B = yd.shape[0]
+            base = per_sample_loss(eng.block_logits(bi, h, yd), y, crit)
+
+            def evaluate(rank_t, p_first, cnt):
+                logits = eng.prefix_logits(bi, kind, h, yd, perm_of(rank_t), pad_rank(rank_t, yd.shape[3]), p_first,
+                                           cnt)
+                yy = y.repeat((cnt,) + (1,) * (y.dim() - 1)) if cnt > 1 else y
+                return per_sample_loss(logits, yy, crit).view(cnt, B)
+
+            return n, B, eng.downstream_elems(bi, tuple(x.shape[1:])), base, evaluate
 
         return prepare
 
@@ -474,6 +500,22 @@ class _RankPadder:
             r = self.cache[id(rank_t)] = (rank_t, torch.cat([rank_t, torch.full(
                 (pad,), self.n + 1, dtype=rank_t.dtype, device=rank_t.device)]))
         return r[1]
+
+
+class _PermOf:
+    """The permutation (int32, on the rank vector's device) a rank vector belongs to: perm[rank[c]] = c
+    (cached per rank vector)."""
+
+    def __init__(self):
+        self.cache = {}
+
+    def __call__(self, rank_t):
+        hit = self.cache.get(id(rank_t))
+        if hit is None or hit[0] is not rank_t:
+            p = torch.empty_like(rank_t)
+            p[rank_t.long()] = torch.arange(rank_t.numel(), dtype=rank_t.dtype, device=rank_t.device)
+            hit = self.cache[id(rank_t)] = (rank_t, p)
+        return hit[1]
 
 
 def _to(t, device):

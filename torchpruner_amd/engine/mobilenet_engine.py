@@ -21,12 +21,18 @@ score as a channel reduction of (y, g), ``tpamd.dwconv_act_dgrad`` (masks g by t
 reduces the post-expand ReLU6's Taylor / Sensitivity partials from the unmasked gradient, masks by
 z), and the expand dgrad with the block's output gradient as ``res=`` when there is a shortcut.
 
+Shapley prefixes are evaluated from inside a block (``forward_to`` / ``prefix_logits`` /
+``logits_from``): the K stacked outputs of the linear project conv are a running rank-1 subtraction
+per pixel (``ops.prefix_project``, csrc/kernels/prefix_project.hip), and the rest of the network runs
+once on them.
+
 Channels are carried zero-padded to a multiple of 32 (``cpad``) as in the ResNet engine, whose conv
 plumbing (packing, tuner, classifier GEMMs, partial-slab arena) this engine inherits. One batch at a
 time: no two-stream pipeline, no graph replay. fp32 throughout.
 """
 from __future__ import annotations
 
+import os
 import weakref
 from dataclasses import dataclass, field
 from typing import Optional
@@ -367,11 +373,123 @@ class MobileNetEngine(ResNetEngine):
             self._arena_sizes[akey] = arena[2]
         return out
 
-    # ------------------------------------------------------------------ not served
-    def locate(self, bn):
-        raise NotImplementedError("Shapley does not run on the MobileNet engine")
+    # ------------------------------------------------------------------ partial forward (Shapley)
+    # Prefix copies of a block's hidden activation are never built. Copy j of the post-depthwise
+    # output y is y with the masked channels set to a per-channel constant ``fill``: 0 when y's own
+    # channels are masked, and clamp(shift, 0, 6) when the post-expand ReLU6's are (a zeroed input
+    # channel leaves the depthwise conv 0 at every pixel, zero padding included, so BN + ReLU6 give
+    # that constant). The project conv is linear, so its K outputs are one conv of the base copy and
+    # a running rank-1 subtraction per pixel (``ops.prefix_project``); the shortcut sits in the base.
+    def locate(self, module):
+        """(block index, "expand" | "dw") of an evaluation module (:meth:`eval_modules`)."""
+        for bi, b in enumerate(self.plan.blocks):
+            if module is b.dw.act:
+                return bi, "dw"
+            if b.expand is not None and module is b.expand.act:
+                return bi, "expand"
+        raise KeyError("not a block ReLU6 of this MobileNet")
 
-    forward_to = logits_from = locate
+    def forward_to(self, x: torch.Tensor, bi: int):
+        """(block ``bi``'s input h, its post-depthwise ReLU6 output y), both in engine layout: the
+        state :meth:`prefix_logits` continues from."""
+        T = ops.require()
+        P = self._pack()
+        h = T.nchw_to_nhwc_pad(x.float().contiguous(), 4)
+        h = self._conv(T, P["stem"], h, False)
+        in_act = _RELU6
+        if not self._stem_fused():
+            h, in_act = h.clamp_(0.0, 6.0), 0
+        for b in range(bi):
+            h = self._block(T, self.plan.blocks[b], P["blocks"][b], h, in_act)
+            in_act = 0
+        blk, e = self.plan.blocks[bi], P["blocks"][bi]
+        if blk.expand is not None:
+            z, in_act = self._conv(T, e["expand"], h, False), _RELU6
+        else:
+            z = h
+        d = e["dw"]
+        y = T.dwconv_act_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, _RELU6, None)
+        return h, y
+
+    def prefix_fill(self, bi: int, kind: str) -> torch.Tensor:
+        """(C_padded,) value a masked channel of block ``bi``'s post-depthwise output takes: zeros
+        for ``"dw"``, clamp(folded depthwise BN shift, 0, 6) for ``"expand"`` (the padded channels'
+        shift is 0, and they are never masked)."""
+        d = self._pack()["blocks"][bi]["dw"]
+        key = "fill_" + kind
+        if key not in d:
+            d[key] = torch.zeros_like(d["shift"]) if kind == "dw" else d["shift"].clamp(0.0, 6.0).contiguous()
+        return d[key]
+
+    def _tail_elems(self, bi: int, H: int, W: int) -> int:
+        """Largest padded per-sample activation from block ``bi``'s (H, W) output to the classifier."""
+        per = H * W * cpad(self.plan.blocks[bi].project.conv.weight.shape[0])
+        for b in self.plan.blocks[bi + 1:]:
+            hid = cpad(b.dw.conv.weight.shape[0])
+            per = max(per, H * W * hid)
+            H, W = _out_hw(b.dw.conv, H, W)
+            per = max(per, H * W * hid, H * W * cpad(b.project.conv.weight.shape[0]))
+        return max(per, H * W * cpad(self.plan.head.conv.weight.shape[0]))
+
+    def downstream_elems(self, bi: int, sample_shape) -> int:
+        """The largest padded per-sample activation downstream of block ``bi``'s output, that output
+        included, for (C, H, W) inputs (Shapley sizes its stacked prefix batch from it)."""
+        H, W = _out_hw(self.plan.stem.conv, *tuple(sample_shape)[-2:])
+        for b in self.plan.blocks[:bi + 1]:
+            H, W = _out_hw(b.dw.conv, H, W)
+        return self._tail_elems(bi, H, W)
+
+    def logits_from(self, bi: int, out: torch.Tensor) -> torch.Tensor:
+        """Logits of the network continued from block ``bi``'s output (possibly K stacked copies
+        along the batch), in slices wherever a tensor would reach 2^31 bytes (as :meth:`max_batch`
+        does for the whole forward)."""
+        T = ops.require()
+        P = self._pack()
+        step = max(1, ((1 << 31) - 1) // (4 * self._tail_elems(bi, out.shape[1], out.shape[2])))
+        logits = []
+        for s in range(0, out.shape[0], step):
+            h = out[s:s + step]
+            for b in range(bi + 1, len(self.plan.blocks)):
+                h = self._block(T, self.plan.blocks[b], P["blocks"][b], h, 0)
+            zh = self._conv(T, P["head"], h, False)
+            logits.append(self._fc(T, P, T.avgpool_nhwc(zh.clamp_(0.0, 6.0))))
+        return logits[0] if len(logits) == 1 else torch.cat(logits, 0)
+
+    def block_logits(self, bi: int, h: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Logits from :meth:`forward_to`'s state, nothing masked."""
+        blk, e = self.plan.blocks[bi], self._pack()["blocks"][bi]
+        return self.logits_from(bi, self._conv(ops.require(), e["project"], y, False, res=h if blk.shortcut else None))
+
+    def prefix_logits(self, bi: int, kind: str, h: torch.Tensor, y: torch.Tensor, perm_t: torch.Tensor,
+                      rank_t: torch.Tensor, p0: int, cnt: int) -> torch.Tensor:
+        """Logits (cnt * B, classes) of the prefixes p0 .. p0+cnt-1 of one permutation: copy j has the
+        channels of rank < p0 + j masked at block ``bi``'s ``kind`` evaluation point. ``perm_t``:
+        int32 (n,) over the real channels; ``rank_t``: its rank vector over the padded width (padding
+        ranks after every real channel). ``TORCHPRUNER_PREFIX_DELTA=0`` (read per call) builds the
+        cnt filled copies and runs the project conv on all of them instead."""
+        T = ops.require()
+        blk, e = self.plan.blocks[bi], self._pack()["blocks"][bi]
+        B, Ho, Wo, C = y.shape
+        fill = self.prefix_fill(bi, kind)
+        res = h if blk.shortcut else None
+        delta = os.environ.get("TORCHPRUNER_PREFIX_DELTA", "1") != "0"
+        co = e["project"]["scale"].numel()
+        # copies per piece: the stacked project output (and, without the delta, input) below 2^31 bytes
+        piece = max(1, ((1 << 31) - 1) // (4 * B * Ho * Wo * (co if delta else max(co, C))))
+        if cnt > piece:
+            return torch.cat([self.prefix_logits(bi, kind, h, y, perm_t, rank_t, p0 + j, min(piece, cnt - j))
+                              for j in range(0, cnt, piece)], 0)
+        if delta:
+            y_base = torch.where((rank_t < p0).view(1, 1, 1, C), fill, y)
+            base = self._conv(T, e["project"], y_base, False, res=res)
+            wt = self._bwd_operands(e["project"])["wt"]  # (C, Cout) with the BN scale folded in
+            out = ops.prefix_project(base.view(B * Ho * Wo, co), y.view(B * Ho * Wo, C), fill, wt, perm_t, p0, cnt)
+            return self.logits_from(bi, out.view(cnt * B, Ho, Wo, co))
+        lim = torch.arange(p0, p0 + cnt, device=y.device, dtype=rank_t.dtype).view(cnt, 1, 1, 1, 1)
+        ys = torch.where(rank_t.view(1, 1, 1, 1, C) < lim, fill, y.unsqueeze(0)).view(cnt * B, Ho, Wo, C)
+        if res is not None and cnt > 1:
+            res = res.repeat(cnt, 1, 1, 1)
+        return self.logits_from(bi, self._conv(T, e["project"], ys, False, res=res))
 
 
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
@@ -379,7 +497,6 @@ _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.Weak
 
 def mobilenet_engine_default() -> bool:
     """``TORCHPRUNER_MOBILENET_ENGINE`` (default 0: the engine is opt-in)."""
-    import os
     return os.environ.get("TORCHPRUNER_MOBILENET_ENGINE", "0") not in ("0", "")
 
 

@@ -16,7 +16,7 @@ from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 __all__ = [
     "available", "backend", "load", "require", "use_native",
     "REDUCE_MODES", "channel_reduce", "column_accumulate", "score_fold_", "channel_fill_", "nan_channels",
-    "gather_multi", "prefix_mask", "shapley_scatter", "shapley_column", "cross_entropy",
+    "gather_multi", "prefix_mask", "prefix_project", "shapley_scatter", "shapley_column", "cross_entropy",
     "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
 ]
 
@@ -154,6 +154,33 @@ def prefix_mask(z: torch.Tensor, rank: torch.Tensor, p0: int, K: int) -> torch.T
     # multiplication would turn inf/NaN into NaN at masked positions; index_fill semantics are exact zeros
     out = torch.where(keep.view(shape) > 0, out, torch.zeros((), dtype=z.dtype, device=z.device))
     return out.reshape((K * z.shape[0],) + tuple(z.shape[1:]))
+
+
+def prefix_project(base: torch.Tensor, a: torch.Tensor, fill: torch.Tensor, wt: torch.Tensor, perm: torch.Tensor,
+                   p0: int, cnt: int) -> torch.Tensor:
+    """The ``cnt`` stacked outputs (cnt, N, Co) of a linear 1x1 conv whose input copies differ by one
+    channel each: copy j is ``a`` (N, C) with the channels perm[0 .. p0+j-1] replaced by ``fill`` (C,),
+    ``base`` (N, Co) the output of copy 0 and ``wt`` (C, Co) the transposed weights:
+
+      out[0] = base;  out[j] = out[j-1] - (a[:, c] - fill[c]) (x) wt[c, :],  c = perm[p0 + j - 1]
+
+    a running rank-1 subtraction in this fixed order (``perm``: int32 (n <= C), p0 + cnt - 1 <= n)."""
+    p0, cnt = int(p0), int(cnt)
+    n, (N, Co), C = perm.numel(), base.shape, a.shape[1]
+    if base.dim() != 2 or a.dim() != 2 or a.shape[0] != N or fill.shape != (C,) or wt.shape != (C, Co) or perm.dim() != 1:
+        raise ValueError("prefix_project: expected base (N, Co), a (N, C), fill (C,), wt (C, Co), perm (n,)")
+    if Co % 4 or n > C or cnt < 1 or p0 < 0 or p0 + cnt - 1 > n:
+        raise ValueError(f"prefix_project: bad arguments (Co {Co}, C {C}, n {n}, p0 {p0}, cnt {cnt})")
+    if use_native(base) and base.dtype == torch.float32:
+        return require().prefix_project(base.contiguous(), a.float().contiguous(), fill.float().contiguous(),
+                                        wt.float().contiguous(), perm.to(base.device, torch.int32).contiguous(), p0, cnt)
+    out = base.new_empty(cnt, N, Co)
+    out[0] = base
+    cols = perm[p0:p0 + cnt - 1].to(base.device, torch.long)
+    for j in range(1, cnt):
+        c = cols[j - 1]
+        out[j] = out[j - 1] - (a[:, c] - fill[c]).unsqueeze(1) * wt[c].unsqueeze(0)
+    return out
 
 
 def shapley_scatter(L: torch.Tensor, perm: torch.Tensor, sv: torch.Tensor, row0: int, k0: int, scale: float) -> None:
