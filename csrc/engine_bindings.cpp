@@ -255,6 +255,84 @@ at::Tensor conv_dgrad(const at::Tensor& g, const c10::optional<at::Tensor>& g_ar
   return out;
 }
 
+// 3x3 / pad-1 conv on 2x2 maps as 9 channel products (conv2x2_fast.hip). x (B,2,2,C); u9 (9,K,C) =
+// G w G^T. Returns out (B,2,2,K), or pooled (B,1,1,K) + argmax bytes.
+std::tuple<at::Tensor, at::Tensor> conv2x2_fast_fwd(const at::Tensor& x, const at::Tensor& u9,
+                                                    const c10::optional<at::Tensor>& scale,
+                                                    const c10::optional<at::Tensor>& shift, bool relu, bool pool,
+                                                    int64_t cfg, int64_t splits) {
+  need(x, "x", 4);
+  need(u9, "u9", 3);
+  const int64_t B = x.size(0), C = x.size(3), K = u9.size(1);
+  TORCH_CHECK(x.size(1) == 2 && x.size(2) == 2, "x must be (B, 2, 2, C)");
+  TORCH_CHECK(u9.size(0) == 9 && u9.size(2) == C, "u9 must be (9, K, C)");
+  TORCH_CHECK(B > 0 && C % 32 == 0 && K % 4 == 0, "C must be a multiple of 32 and K of 4");
+  TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const float* sc = opt_ptr(scale, K, "scale");
+  const float* sh = opt_ptr(shift, K, "shift");
+  const int64_t sp = tp_conv_norm_splits((int)std::max<int64_t>(1, std::min<int64_t>(splits, 1 << 16)), (int)C);
+  at::Tensor out, am;
+  if (pool) {
+    out = at::empty({B, 1, 1, K}, x.options());
+    am = at::empty({B, 1, 1, K}, x.options().dtype(at::kByte));
+  } else {
+    out = at::empty({B, 2, 2, K}, x.options());
+  }
+  // workspaces from the caching allocator (capturable in a HIP graph, like the split-K slabs)
+  at::Tensor V = at::empty({9, B, C}, x.options()), slabs = at::empty({9 * sp, B, K}, x.options());
+  TP_CHECK_HIP(tp_conv2x2_fast_fwd(x.data_ptr<float>(), u9.data_ptr<float>(), (int)B, (int)C, (int)K, (int)cfg,
+                                   (int)sp, sc, sh, relu ? 1 : 0, pool ? 1 : 0, out.data_ptr<float>(),
+                                   pool ? am.data_ptr<uint8_t>() : nullptr, V.data_ptr<float>(),
+                                   slabs.data_ptr<float>(), cur_stream()));
+  return {out, am};
+}
+
+// Its data gradient with the conv_dgrad epilogue contract (tay_group = Cin: taylor is (4, B, Cin), one
+// slot per pixel, accumulated). g (B,2,2,Cg), or the pooled (B,1,1,Cg) with g_argmax; u9t (9,Cin,Cg).
+at::Tensor conv2x2_fast_dgrad(const at::Tensor& g, const c10::optional<at::Tensor>& g_argmax, const at::Tensor& u9t,
+                              const at::Tensor& act, const c10::optional<at::Tensor>& bn_scale,
+                              const c10::optional<at::Tensor>& taylor, bool want_out, int64_t cfg, int64_t splits,
+                              int64_t tay_mode) {
+  need(g, "g", 4);
+  need(u9t, "u9t", 3);
+  need(act, "act", 4);
+  const bool unpool = g_argmax.has_value() && g_argmax->defined();
+  const int64_t B = act.size(0), Cin = act.size(3), Cg = g.size(3);
+  TORCH_CHECK(act.size(1) == 2 && act.size(2) == 2, "act must be (B, 2, 2, Cin)");
+  if (unpool) {
+    TORCH_CHECK(g.size(1) == 1 && g.size(2) == 1, "pooled grad shape mismatch");
+    TORCH_CHECK(g_argmax->scalar_type() == at::kByte && g_argmax->sizes() == g.sizes() && g_argmax->is_contiguous() &&
+                    g_argmax->is_cuda(), "g_argmax must be uint8 with g's shape");
+  } else {
+    TORCH_CHECK(g.size(1) == 2 && g.size(2) == 2, "grad shape mismatch");
+  }
+  TORCH_CHECK(g.size(0) == B && B > 0, "batch mismatch");
+  TORCH_CHECK(u9t.size(0) == 9 && u9t.size(1) == Cin && u9t.size(2) == Cg, "u9t must be (9, Cin, Cg)");
+  TORCH_CHECK(Cg % 32 == 0 && Cin % 4 == 0, "Cg must be a multiple of 32 and Cin of 4");
+  TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
+  TORCH_CHECK(tay_mode >= 0 && tay_mode <= 2, "bad tay_mode");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale");
+  float* tay = nullptr;
+  if (taylor.has_value() && taylor->defined()) {
+    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
+                    taylor->numel() == 4 * B * Cin, "taylor must be a contiguous float32 (4, B, Cin) GPU tensor");
+    tay = taylor->data_ptr<float>();
+  }
+  TORCH_CHECK(want_out || tay, "nothing to compute: no output and no taylor slab");
+  at::Tensor out;
+  if (want_out) out = at::empty({B, 2, 2, Cin}, g.options());
+  const int64_t sp = tp_conv_norm_splits((int)std::max<int64_t>(1, std::min<int64_t>(splits, 1 << 16)), (int)Cg);
+  at::Tensor V = at::empty({9, B, Cg}, g.options()), slabs = at::empty({9 * sp, B, Cin}, g.options());
+  TP_CHECK_HIP(tp_conv2x2_fast_dgrad(g.data_ptr<float>(), unpool ? g_argmax->data_ptr<uint8_t>() : nullptr,
+                                     u9t.data_ptr<float>(), (int)B, (int)Cg, (int)Cin, (int)cfg, (int)sp,
+                                     act.data_ptr<float>(), sc, tay, (int)tay_mode,
+                                     want_out ? out.data_ptr<float>() : nullptr, V.data_ptr<float>(),
+                                     slabs.data_ptr<float>(), cur_stream()));
+  return out;
+}
+
 // First conv layer (tiny Cin) on the VALU: NCHW input -> NHWC output, BN affine + ReLU fused.
 // ``wt``: optional tap-major copy of w, [Cin][3][3][Cout], packed once by the caller (the
 // wave-uniform kernel's operand layout); built here per call when absent.
@@ -1237,6 +1315,10 @@ void register_engine_ops_def(torch::Library& m) {
         "int splits, Tensor(a!)? apoz=None, float slope=0.0) -> (Tensor, Tensor)");
   m.def("conv_dgrad(Tensor g, Tensor? g_argmax, Tensor wt, Tensor act, Tensor? bn_scale, Tensor(a!)? taylor, "
         "bool want_out, int ks, int cfg, int splits, int tay_group=0, int tay_mode=0, float slope=0.0) -> Tensor");
+  m.def("conv2x2_fast_fwd(Tensor x, Tensor u9, Tensor? scale, Tensor? shift, bool relu, bool pool, int cfg, "
+        "int splits) -> (Tensor, Tensor)");
+  m.def("conv2x2_fast_dgrad(Tensor g, Tensor? g_argmax, Tensor u9t, Tensor act, Tensor? bn_scale, "
+        "Tensor(a!)? taylor, bool want_out, int cfg, int splits, int tay_mode=0) -> Tensor");
   m.def("conv_first(Tensor x, Tensor w, Tensor scale, Tensor shift, bool relu, Tensor? wt=None) -> Tensor");
   m.def("wino_weights(Tensor w, bool flip_t, int K=0, int C=0, bool bf16=False) -> Tensor");
   m.def("prefix_tri_operands(Tensor z, Tensor w, Tensor perm, int p0, int cnt, int Kc) -> (Tensor, Tensor)");
@@ -1255,6 +1337,8 @@ void register_engine_ops_def(torch::Library& m) {
 void register_engine_ops_impl(torch::Library& m) {
   m.impl("conv_fwd", &conv_fwd);
   m.impl("conv_dgrad", &conv_dgrad);
+  m.impl("conv2x2_fast_fwd", &conv2x2_fast_fwd);
+  m.impl("conv2x2_fast_dgrad", &conv2x2_fast_dgrad);
   m.impl("conv_first", &conv_first);
   m.impl("prefix_tri_operands", &prefix_tri_operands);
   m.impl("wino_weights", &wino_weights);

@@ -61,6 +61,18 @@ int tp_dwconv_act_tay_slots(int H, int W, int C);
 hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
                                float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
                                int pad, int in_act, int out_act, hipStream_t st);
+// conv_mfma.hip: nbatch independent GEMMs slab[i * splits + s] (M, N) = K range s of x[i] (M, K) . w[i] (N, K)^T
+int tp_conv_norm_splits(int splits, int K);
+hipError_t tp_conv_igemm_batched(const float* x, const float* w, int nbatch, int M, int K, int N, int cfg, int splits,
+                                 float* slabs, hipStream_t st);
+// conv2x2_fast.hip: 3x3 / pad-1 conv on 2x2 maps as 9 channel products (u9 (9, Cout, Cin) = G w G^T);
+// V (9, B, Cin) and slabs (9 * splits, B, Cout) are workspaces
+hipError_t tp_conv2x2_fast_fwd(const float* x, const float* u9, int B, int C, int K, int cfg, int splits,
+                               const float* scale, const float* shift, int relu, int pool, float* out,
+                               uint8_t* out_argmax, float* V, float* slabs, hipStream_t st);
+hipError_t tp_conv2x2_fast_dgrad(const float* g, const uint8_t* g_argmax, const float* u9t, int B, int Cg, int Cin,
+                                 int cfg, int splits, const float* act, const float* bn_scale, float* taylor,
+                                 int tay_mode, float* out, float* V, float* slabs, hipStream_t st);
 // data_ops.hip
 hipError_t tp_augment_u8(const uint8_t* src, const int64_t* idx, const int* aug, int B, int C, int H, int W, int pad,
                          const float* mean, const float* inv_std, float* out, hipStream_t st);

@@ -104,6 +104,11 @@ struct ConvArgs {
   const float* bnb_mean;    // [M][N], batch mean / invstd [N] and its ReLU bit mask (nullable: no
   const float* bnb_invstd;  // ReLU); the tile sums become (sum gm, sum gm * xhat), gm = the masked
   const uint8_t* bnb_bits;  // gradient, xhat = (y - mean) * invstd: that BN's backward statistics
+  // batched GEMM (GEN 0; see tp_conv_igemm_batched): bsplits > 0 -> grid.y carries (batch, split) as
+  // batch * bsplits + split; batch i reads x + i * x_bstride and w + i * w_bstride (elements) and
+  // EPI_PARTIAL writes raw slab number blockIdx.y
+  int bsplits;
+  long long x_bstride, w_bstride;
 };
 
 // one ReLU bit-mask nibble (channels n..n+3 of pixel pix, N % 4 == 0) applied to a quad
@@ -262,15 +267,22 @@ __global__ __launch_bounds__(tile_threads(BM, BN, WM, WN), tile_threads(BM, BN, 
     }
   }
   const int kt_total = GEN == 3 ? __builtin_popcount(tmask) * cin_tiles : p.K / BK;
-  const int kt_begin = sk_mode ? sk_kb : GEN == 3 ? 0 : split * p.k_tiles_per_split;
+  int batch = 0, ksplit = split;  // batched GEMM: ``split`` (grid.y) = batch * bsplits + K split
+  if constexpr (GEN == 0) {
+    if (p.bsplits > 0) {
+      batch = split / p.bsplits;
+      ksplit = split - batch * p.bsplits;
+    }
+  }
+  const int kt_begin = sk_mode ? sk_kb : GEN == 3 ? 0 : ksplit * p.k_tiles_per_split;
   const int kt_end = sk_mode ? sk_ke : GEN == 3 ? kt_total : min(kt_total, kt_begin + p.k_tiles_per_split);
 
   // ---- per-thread A rows: loop-invariant offsets + a bitmask of in-bounds taps ----------
   // Loads go through buffer descriptors: an out-of-range offset returns zeros in hardware,
   // so conv padding and ragged M/N edges cost one v_cndmask instead of a branch per load.
   constexpr unsigned OOB = 0x80000000u;
-  const i32x4 xr = make_rsrc(p.x, (unsigned)(p.x_elems * 4));
-  const i32x4 wr = make_rsrc(p.w, (unsigned)(p.N * p.K * 4));
+  const i32x4 xr = make_rsrc(p.x + batch * p.x_bstride, (unsigned)(p.x_elems * 4));
+  const i32x4 wr = make_rsrc(p.w + batch * p.w_bstride, (unsigned)(p.N * p.K * 4));
   const i32x4 amr = make_rsrc(p.x_argmax, UNPOOL ? (unsigned)p.x_elems : 0u);
 
   int a_off[T::A_CHUNKS], a_row[T::A_CHUNKS], a_c4[T::A_CHUNKS];
@@ -1391,6 +1403,49 @@ extern "C" hipError_t tp_conv_igemm(const float* x, const uint8_t* x_argmax, con
   else if (epi == EPI_BWD) conv_epilogue<EPI_BWD><<<grid, 256, 0, st>>>(a, ws, splits);
   else return hipErrorInvalidValue;
   return hipGetLastError();
+}
+
+// ``splits`` as the launchers normalise it for K = 32 * kt: no empty K range
+extern "C" int tp_conv_norm_splits(int splits, int K) {
+  const int kt = K / 32;
+  if (kt < 1) return 1;
+  splits = std::max(1, std::min(splits, kt));
+  const int per = (kt + splits - 1) / splits;
+  return (kt + per - 1) / per;
+}
+
+// ``nbatch`` independent GEMMs in one launch: slab[i * splits + s] (M, N) = the K range s of
+// x[i] (M, K) . w[i] (N, K)^T, raw (EPI_PARTIAL), for the caller's combine. x (nbatch, M, K),
+// w (nbatch, N, K), slabs (nbatch * splits, M, N); ``splits`` already normalised (tp_conv_norm_splits).
+extern "C" hipError_t tp_conv_igemm_batched(const float* x, const float* w, int nbatch, int M, int K, int N, int cfg,
+                                            int splits, float* slabs, hipStream_t st) {
+  using namespace tp;
+  if (!x || !w || !slabs || nbatch < 1 || M < 1 || N < 1 || K < 32 || K % 32 != 0 || cfg < 0 || cfg > 6 ||
+      splits < 1 || splits != tp_conv_norm_splits(splits, K) || (long long)nbatch * splits > 65535)
+    return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(slabs)) & 15)
+    return hipErrorInvalidValue;
+  // buffer descriptors address 32-bit byte offsets (per batch); tile indices are 32-bit
+  if ((long long)M * K >= (1ll << 29) || (long long)N * K >= (1ll << 29) || (long long)M * N >= (1ll << 31))
+    return hipErrorInvalidValue;
+  ConvArgs a{};
+  a.x = x;
+  a.w = w;
+  a.B = M;
+  a.H = a.W = a.Ho = a.Wo = 1;
+  a.Cin = K;
+  a.N = N;
+  a.K = K;
+  a.M = M;
+  a.x_elems = (long long)M * K;
+  a.k_tiles_per_split = (K / 32 + splits - 1) / splits;
+  a.out = slabs;
+  a.HWo = 1;
+  a.stride = 1;
+  a.bsplits = splits;
+  a.x_bstride = (long long)M * K;
+  a.w_bstride = (long long)N * K;
+  return launch_any<1, false, false, EPI_PARTIAL>(cfg, a, nbatch * splits, st);
 }
 
 // Split combine + epilogue for slabs produced elsewhere (Winograd partials): slab layout

@@ -300,6 +300,33 @@ def build_prefix_project_sanitizer(verbose: bool = False) -> Path:
     return exe
 
 
+def build_conv2x2_fast_sanitizer(verbose: bool = False) -> Path:
+    """Build ``csrc/tests/conv2x2_fast_validation.cpp`` against the nine-product 2x2-map conv
+    launchers (``conv2x2_fast.hip``, and ``conv_mfma.hip`` for the batched GEMM they call; its object
+    is the one :func:`build_host_sanitizer` makes) with AddressSanitizer + UBSan on the HOST code
+    only, like :func:`build_prefix_project_sanitizer`. Returns the executable path."""
+    out_dir = ROOT / "build" / "asan"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    headers = sorted((CSRC / "include").glob("*.h"))
+    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    jobs, objs = [], []
+    for name in ("conv_mfma", "conv2x2_fast"):
+        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
+        objs.append(obj)
+        if _needs_rebuild(src, obj, headers):
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
+                         "-c", src, "-o", obj])
+    test_src, test_obj = CSRC / "tests" / "conv2x2_fast_validation.cpp", out_dir / "conv2x2_fast_validation.o"
+    if _needs_rebuild(test_src, test_obj, headers):
+        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san, "-c", test_src, "-o", test_obj])
+    with ThreadPoolExecutor(max_workers=3) as ex:
+        list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / "conv2x2_fast_validation"
+    if jobs or not exe.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
+    return exe
+
+
 def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
     """Build ``csrc/tests/dwconv_carried_validation.cpp`` against the carried-width depthwise-conv
     launchers (``dwconv.hip``) and the BatchNorm launchers (``batchnorm.hip``) with

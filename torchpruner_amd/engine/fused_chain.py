@@ -64,6 +64,8 @@ CFG_SK = 32  # tile-config flag of the GEN implicit GEMM: stream-K (conv_mfma.hi
 CFG_SB = 64  # tile-config flag: single-buffered LDS stage (GEN 1 1x1 forward, one K pass; short-K convs)
 CFG_RED = 1 << 12  # tuner-only flag (never passed to a kernel): a plain dgrad + the separate channel reduction
 CFG_BF16 = 256  # tile-config flag of conv_igemm: bf16 operands / fp32 accumulation (opt-in, compute_dtype)
+FAST2 = 200  # pseudo cfg offset: 2x2-map conv as nine batched channel products (conv2x2_fast.hip) on
+             # implicit-GEMM tile config cfg - FAST2
 _BF16_CFGS = (0, 2, 3)  # the implicit-GEMM tiles built with bf16 variants (conv_mfma.hip launch_any)
             # than F(2x2); dgrads of pooled layers take the explicit unpool first
 
@@ -88,6 +90,26 @@ def winograd_weights(w: torch.Tensor) -> torch.Tensor:
     img = u.permute(1, 4, 0, 3, 6, 2, 5).contiguous()
     img[:, :, :, :, 8:] = img[:, :, :, :, 8:, [2, 3, 0, 1]]
     return img.reshape(C // 8, K // 32, 4096).float().contiguous()
+
+
+# 2x2-map conv as 9 channel products (conv2x2_fast.hip): weight transform U = G w G^T on taps
+# [W0, W1, W2], input transform Bt, output transform At (nested 2x2 Toeplitz products, 3 mults each)
+_G2 = ((0.0, 1.0, 0.0), (0.0, -1.0, 1.0), (1.0, -1.0, 0.0))
+_BT2 = ((1.0, 1.0), (0.0, 1.0), (1.0, 0.0))
+_AT2 = ((1.0, 1.0, 0.0), (1.0, 0.0, 1.0))
+
+
+@torch.no_grad()
+def fast2x2_weights(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
+    """(K, C, 3, 3) conv weight -> U9 (9, K, C), U9[3i + j][k][c] = (G w[k][c] G^T)[i][j]: the nine
+    (output rows, input channels) GEMM operands of the 2x2-map conv. ``dgrad``: of the flipped,
+    transposed weight (the data gradient's operand, (9, C, K)). Computed in fp64, rounded once."""
+    assert w.dim() == 4 and w.shape[2:] == (3, 3), "fast2x2_weights needs (K, C, 3, 3) kernels"
+    if dgrad:
+        w = w.flip(2, 3).transpose(0, 1)
+    G = torch.tensor(_G2, dtype=torch.float64, device=w.device)
+    u = torch.einsum("ia,kcab,jb->ijkc", G, w.double(), G)
+    return u.reshape(9, w.shape[0], w.shape[1]).float().contiguous()
 
 
 def taylor_slots(H: int, W: int) -> int:
@@ -328,7 +350,8 @@ _KIND_NAMES = {WINO: "wino2_direct", WINO_LDS: "wino2", WINO_UNP: "wino2_unpool"
 
 def kernel_name(cfg: int) -> str:
     """Readable name of a tuner choice: a Winograd kind, ``igemm<tile>`` (``_TILES``), ``dense2x2``
-    igemm (2x2 layers as one dense GEMM), ``bf16`` igemm variants, or a persistent 1x1 GEMM."""
+    igemm (2x2 layers as one dense GEMM), ``fast2x2`` igemm (2x2 layers as nine batched channel
+    products), ``bf16`` igemm variants, or a persistent 1x1 GEMM."""
     if cfg in _KIND_NAMES:
         return _KIND_NAMES[cfg]
     if cfg >= CFG_RED:
@@ -337,6 +360,9 @@ def kernel_name(cfg: int) -> str:
         return kernel_name(cfg - CFG_SK) + "_streamk"
     if CFG_SB <= cfg < CFG_SB + 7:
         return kernel_name(cfg - CFG_SB) + "_1stage"
+    if FAST2 <= cfg < FAST2 + 7:
+        bm, bn = _TILES[cfg - FAST2]
+        return f"fast2x2_igemm{bm}x{bn}"
     if cfg >= 100 and cfg < CFG_BF16:
         bm, bn = _TILES.get(cfg - 100, (0, 0))
         return f"dense2x2_igemm{bm}x{bn}"
@@ -655,6 +681,35 @@ class FusedChainEngine:
         return d
 
     @staticmethod
+    def _u9(e, dgrad=False):
+        """U9 = G w G^T operands of the nine-product 2x2-map conv (forward, or the flipped/transposed
+        data-gradient operand), built on first use and cached in the packed entry."""
+        key = "u9t" if dgrad else "u9"
+        u = e.get(key)
+        if u is None:
+            u = e[key] = fast2x2_weights(e["w4d"], dgrad)
+        return u
+
+    @staticmethod
+    def _fast2_cands(B, N, C):
+        """Nine-product candidates of a 2x2-map conv (B x C).(C x N) x 9: every implicit-GEMM tile in
+        one K pass and with the split-K that fills the chip (nine batches quantise badly on 256 CUs:
+        128x128 tiles of B=2048, N=512 are 576 blocks, so a 2-way split is offered as well)."""
+        out = []
+        for cfg, (bm, bn) in _TILES.items():
+            if N <= 64 and bn == 128:
+                continue
+            tiles = 9 * math.ceil(B / bm) * math.ceil(N / bn)
+            sp, kt = 1, C // 32
+            while tiles * sp < 2 * _CU and sp * 2 <= kt // 4 and sp < 16:
+                sp *= 2
+            sps = {sp, max(1, sp // 2), 1}
+            if sp == 1 and kt >= 8:
+                sps.add(2)
+            out += [(FAST2 + cfg, s_) for s_ in sorted(sps)]
+        return out
+
+    @staticmethod
     def _ubf(e, dgrad=False):
         """bf16 F(2x2) U images (the WINO_BF kernels) of the entry's weight, built on first use."""
         key = "utb" if dgrad else "ub"
@@ -687,6 +742,12 @@ class FusedChainEngine:
                                     _W4_VARIANT[cfg])
         if cfg in (WINO, WINO_LDS):
             return T.conv_wino_fwd(h, e["u"], e["scale"], e["shift"], True, e["pool"], sp, cfg == WINO_LDS, apoz)
+        if cfg >= FAST2:
+            if apoz is None:  # the pool (value + argmax byte) is part of the combine
+                return T.conv2x2_fast_fwd(h, self._u9(e), e["scale"], e["shift"], True, e["pool"], cfg - FAST2, sp)
+            y, _ = T.conv2x2_fast_fwd(h, self._u9(e), e["scale"], e["shift"], True, False, cfg - FAST2, sp)
+            apoz += ops.channel_reduce(y.permute(0, 3, 1, 2), None, "apoz")
+            return T.maxpool2_nhwc(y) if e["pool"] else (y, None)
         if cfg >= self.DENSE:
             d = self._dense(e)
             B, N = h.shape[0], e["scale"].numel()
@@ -710,7 +771,7 @@ class FusedChainEngine:
                 cands = self._wino_bf_cands(T, B, H, W, N, C) + cands
         elif H == 2 and W == 2 and C % 32 == 0:
             cands = [(self.DENSE + c, s_) for c, s_ in TUNER.candidates(B, 4 * N, 4 * C)] + \
-                TUNER.candidates(M, N, K, wino)
+                TUNER.candidates(M, N, K, wino) + self._fast2_cands(B, N, C)
         elif self.use_wino and _wino4_ok(H, W, C, N) and "w4d" in e:
             cands = _wino4_cands(B, H, W, N, C) + TUNER.candidates(M, N, K, wino)  # [0] = the untuned pick
         cfg, sp = TUNER.choose(("fwd", tuple(h.shape), N, e["pool"], wino is not None, self.bf16), M, N, K,
@@ -744,6 +805,9 @@ class FusedChainEngine:
                                      tay_mode=tm)
         if cfg in (WINO, WINO_LDS):
             return T.conv_wino_dgrad(g, am, e["ut"], act, sc, taylor, want_out, sp, cfg == WINO_LDS, tay_mode=tm)
+        if cfg >= FAST2:  # a pooled gradient is unpooled by the input transform
+            out = T.conv2x2_fast_dgrad(g, am, self._u9(e, True), act, sc, taylor, want_out, cfg - FAST2, sp, tm)
+            return out if want_out else None
         if cfg >= self.DENSE:
             d = self._dense(e)
             if am is not None:
@@ -1189,7 +1253,7 @@ class FusedChainEngine:
                     sc4 = pe["scale4"] = sc_prev.repeat(4).contiguous()
                 # dense GEMM dgrad: one writer per Taylor element (deterministic as well)
                 cands = [(self.DENSE + c, s_) for c, s_ in TUNER.candidates(B, 4 * Cin, 4 * Cg)] + \
-                    TUNER.candidates(M, Cin, e["wt"].shape[1], wino, True)
+                    TUNER.candidates(M, Cin, e["wt"].shape[1], wino, True) + self._fast2_cands(B, Cin, Cg)
             elif wino is not None and am is not None:
                 wc = TUNER.candidates(M, Cin, e["wt"].shape[1], wino, True)
                 wc = [c for c in wc if c[0] == WINO_LDS] + [c for c in wc if c[0] != WINO_LDS]
@@ -1226,7 +1290,7 @@ class FusedChainEngine:
         return res
 
 
-KERNEL_FAMILIES = ("wino4", "wino4_fused", "wino4_m3", "wino2", "wino2_direct", "igemm", "wino2_bf16")
+KERNEL_FAMILIES = ("wino4", "wino4_fused", "wino4_m3", "wino2", "wino2_direct", "igemm", "wino2_bf16", "fast2x2")
 
 
 def family_policy(family: str, split: str = "min"):
@@ -1235,7 +1299,8 @@ def family_policy(family: str, split: str = "min"):
     pooled blocks unpooling in their epilogue, ``wino4_m3`` its MODE 3 kernel, ``wino2`` F(2x2,3x3) LDS-staged (+ explicit unpool), ``wino2_direct``
     F(2x2) with direct patch loads, ``igemm`` the implicit GEMM (dense 2x2 GEMM, VALU first
     layer; with bf16 operands the bf16 implicit GEMM), ``wino2_bf16`` the bf16 F(2x2) kernels
-    (compute_dtype=bfloat16 only). ``split``: the fewest ("min") or most ("max") channel splits of
+    (compute_dtype=bfloat16 only), ``fast2x2`` the nine-product kernels of the 2x2-map layers
+    (conv2x2_fast.hip). ``split``: the fewest ("min") or most ("max") channel splits of
     that family. Layers the family does not cover keep the untuned pick."""
     eng = FusedChainEngine
 
@@ -1252,7 +1317,9 @@ def family_policy(family: str, split: str = "min"):
         if family == "wino2_direct":
             return k == WINO
         if family == "igemm":
-            return 0 <= k <= 6 or eng.DENSE <= k or k == eng.FIRST_DIRECT
+            return 0 <= k <= 6 or eng.DENSE <= k < FAST2 or CFG_BF16 <= k or k == eng.FIRST_DIRECT
+        if family == "fast2x2":
+            return FAST2 <= k < FAST2 + 7
         if family == "wino2_bf16":
             return k in (WINO_BF, WINO_BF_UNP)
         raise ValueError(f"unknown kernel family {family!r}")
