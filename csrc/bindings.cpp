@@ -559,9 +559,173 @@ at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
   return dx;
 }
 
+// ---- squeeze-and-excitation gates (squeeze_excite.hip): x / g (B, H, W, C) NHWC, rows (B, C) / (B, Cs)
+void check_se_act(const at::Tensor& x, const char* name) {
+  check_cuda_f32(x, name);
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, name, " must be a non-empty contiguous NHWC tensor");
+  TORCH_CHECK(x.numel() < (int64_t(1) << 29), name, " exceeds the kernels' 2 GiB operand range");
+  TORCH_CHECK(x.size(0) <= 65535, name, ": more than 65535 images per call");
+}
+
+void check_se_rows(const at::Tensor& t, int64_t B, int64_t n, const at::Tensor& like, const char* name) {
+  check_cuda_f32(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == B && t.size(1) == n && t.is_contiguous() && t.device() == like.device(),
+              name, " must be a contiguous (", B, ", ", n, ") tensor on the same device");
+}
+
+// fc weights in the parameter's layout: (out, in) or (out, in, 1, 1), contiguous
+void check_se_weight(const at::Tensor& w, int64_t n_out, int64_t n_in, const at::Tensor& like, const char* name) {
+  check_cuda_f32(w, name);
+  TORCH_CHECK((w.dim() == 2 || (w.dim() == 4 && w.size(2) == 1 && w.size(3) == 1)) && w.size(0) == n_out &&
+                  w.size(1) == n_in && w.is_contiguous() && w.device() == like.device(),
+              name, " must be a contiguous (", n_out, ", ", n_in, "[, 1, 1]) weight on the same device");
+}
+
+const float* se_bias(const c10::optional<at::Tensor>& b, int64_t n, const at::Tensor& like, const char* name) {
+  if (!b.has_value() || !b->defined()) return nullptr;
+  check_cuda_f32(*b, name);
+  TORCH_CHECK(b->dim() == 1 && b->size(0) == n && b->is_contiguous() && b->device() == like.device(), name,
+              " must be a contiguous (", n, ",) tensor on the same device");
+  return b->data_ptr<float>();
+}
+
+void check_se_widths(int64_t C, int64_t Cs) {
+  TORCH_CHECK(C >= 1 && Cs >= 1 && C + Cs <= 12288, "gate widths out of the kernels' range (C + Cs <= 12288), got ", C,
+              " and ", Cs);
+}
+
+// (B, C) = scale * sum over the pixels of a (* x when given)
+at::Tensor se_reduce(const at::Tensor& a, const at::Tensor* x) {
+  const int64_t B = a.size(0), HW = a.size(1) * a.size(2), C = a.size(3);
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  auto out = at::empty({B, C}, a.options());
+  const int splits = tp_se_splits((int)B, (int)HW, (int)C);
+  at::Tensor ws;
+  if (splits > 1) ws = at::empty({(int64_t)splits * B * C}, a.options());
+  float* wp = splits > 1 ? ws.data_ptr<float>() : nullptr;
+  if (x != nullptr)
+    TP_CHECK_HIP(tp_se_bwd_reduce(a.data_ptr<float>(), x->data_ptr<float>(), out.data_ptr<float>(), wp, splits, (int)B,
+                                  (int)HW, (int)C, cur_stream()));
+  else
+    TP_CHECK_HIP(tp_se_pool(a.data_ptr<float>(), out.data_ptr<float>(), wp, splits, (int)B, (int)HW, (int)C,
+                            cur_stream()));
+  return out;
+}
+
+at::Tensor se_pool(const at::Tensor& x) {
+  check_se_act(x, "x");
+  return se_reduce(x, nullptr);
+}
+
+at::Tensor se_bwd_reduce(const at::Tensor& g, const at::Tensor& x) {
+  check_se_act(g, "g");
+  check_se_act(x, "x");
+  TORCH_CHECK(g.sizes() == x.sizes() && g.device() == x.device(), "g / x shape or device mismatch");
+  return se_reduce(g, &x);
+}
+
+std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Tensor& w1,
+                                               const c10::optional<at::Tensor>& b1, const at::Tensor& w2,
+                                               const c10::optional<at::Tensor>& b2, int64_t gate) {
+  check_cuda_f32(p, "p");
+  TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && p.numel() > 0, "p must be a non-empty contiguous (B, C) tensor");
+  TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
+  const int64_t B = p.size(0), C = p.size(1);
+  TORCH_CHECK(w1.dim() >= 2, "w1 must be a (Cs, C[, 1, 1]) weight");
+  const int64_t Cs = w1.size(0);
+  check_se_widths(C, Cs);
+  check_se_weight(w1, Cs, C, p, "w1");
+  check_se_weight(w2, C, Cs, p, "w2");
+  const float* b1p = se_bias(b1, Cs, p, "b1");
+  const float* b2p = se_bias(b2, C, p, "b2");
+  TORCH_CHECK(B * std::max(C, Cs) < (int64_t(1) << 24), "too many rows");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
+  auto h = at::empty({B, Cs}, p.options());
+  auto s = at::empty({B, C}, p.options());
+  TP_CHECK_HIP(tp_se_gate_fwd(p.data_ptr<float>(), w1.data_ptr<float>(), b1p, w2.data_ptr<float>(), b2p,
+                              h.data_ptr<float>(), s.data_ptr<float>(), (int)B, (int)C, (int)Cs, (int)gate,
+                              cur_stream()));
+  return {h, s};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_bwd(const at::Tensor& ds, const at::Tensor& s,
+                                                           const at::Tensor& h, const at::Tensor& w1,
+                                                           const at::Tensor& w2, int64_t gate) {
+  check_cuda_f32(ds, "ds");
+  TORCH_CHECK(ds.dim() == 2 && ds.is_contiguous() && ds.numel() > 0, "ds must be a non-empty contiguous (B, C) tensor");
+  TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
+  TORCH_CHECK(h.dim() == 2, "h must be (B, Cs)");
+  const int64_t B = ds.size(0), C = ds.size(1), Cs = h.size(1);
+  check_se_widths(C, Cs);
+  check_se_rows(s, B, C, ds, "s");
+  check_se_rows(h, B, Cs, ds, "h");
+  check_se_weight(w1, Cs, C, ds, "w1");
+  check_se_weight(w2, C, Cs, ds, "w2");
+  TORCH_CHECK(B * std::max(C, Cs) < (int64_t(1) << 24), "too many rows");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(ds.device());
+  auto dz2 = at::empty({B, C}, ds.options());
+  auto dz1 = at::empty({B, Cs}, ds.options());
+  auto dp = at::empty({B, C}, ds.options());
+  TP_CHECK_HIP(tp_se_gate_bwd(ds.data_ptr<float>(), s.data_ptr<float>(), h.data_ptr<float>(), w1.data_ptr<float>(),
+                              w2.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr<float>(), dp.data_ptr<float>(),
+                              (int)B, (int)C, (int)Cs, (int)gate, cur_stream()));
+  return {dz2, dz1, dp};
+}
+
+at::Tensor se_scale(const at::Tensor& x, const at::Tensor& s) {
+  check_se_act(x, "x");
+  const int64_t B = x.size(0), C = x.size(3);
+  check_se_rows(s, B, C, x, "s");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto out = at::empty_like(x);
+  TP_CHECK_HIP(tp_se_scale(x.data_ptr<float>(), s.data_ptr<float>(), out.data_ptr<float>(), (int)B,
+                           (int)(x.size(1) * x.size(2)), (int)C, cur_stream()));
+  return out;
+}
+
+at::Tensor se_bwd_dx(const at::Tensor& g, const at::Tensor& s, const at::Tensor& dp) {
+  check_se_act(g, "g");
+  const int64_t B = g.size(0), C = g.size(3);
+  check_se_rows(s, B, C, g, "s");
+  check_se_rows(dp, B, C, g, "dp");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  auto dx = at::empty_like(g);
+  TP_CHECK_HIP(tp_se_bwd_dx(g.data_ptr<float>(), s.data_ptr<float>(), dp.data_ptr<float>(), dx.data_ptr<float>(),
+                            (int)B, (int)(g.size(1) * g.size(2)), (int)C, cur_stream()));
+  return dx;
+}
+
+// dW[r, k] = sum_b a[b, r] * m[b, k] written into ``dw`` ((R, K) or (R, K, 1, 1)) with that tensor's own
+// strides (the parameter's: DDP bucket views); returns db[r] = sum_b a[b, r] when asked for
+c10::optional<at::Tensor> se_wgrad(const at::Tensor& a, const at::Tensor& m, at::Tensor& dw, bool want_bias) {
+  check_cuda_f32(a, "a");
+  check_cuda_f32(dw, "dw");
+  TORCH_CHECK(a.dim() == 2 && a.is_contiguous() && a.numel() > 0 && m.dim() == 2, "a / m must be (B, R) / (B, K) rows");
+  const int64_t B = a.size(0), R = a.size(1), K = m.size(1);
+  check_se_rows(m, B, K, a, "m");
+  TORCH_CHECK((dw.dim() == 2 || (dw.dim() == 4 && dw.size(2) == 1 && dw.size(3) == 1)) && dw.size(0) == R &&
+                  dw.size(1) == K && dw.device() == a.device() && dw.stride(0) > 0 && dw.stride(1) > 0,
+              "dw must be a (R, K[, 1, 1]) tensor with positive strides on the same device");
+  TORCH_CHECK(R * K < (int64_t(1) << 29) && B * std::max(R, K) < (int64_t(1) << 29), "operands exceed the 2 GiB range");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  c10::optional<at::Tensor> db;
+  if (want_bias) db = at::empty({R}, a.options());
+  TP_CHECK_HIP(tp_se_wgrad(a.data_ptr<float>(), m.data_ptr<float>(), dw.data_ptr<float>(),
+                           want_bias ? db->data_ptr<float>() : nullptr, (int)B, (int)R, (int)K, dw.stride(0),
+                           dw.stride(1), cur_stream()));
+  return db;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(tpamd, m) {
+  m.def("se_pool(Tensor x) -> Tensor");
+  m.def("se_gate_fwd(Tensor p, Tensor w1, Tensor? b1, Tensor w2, Tensor? b2, int gate) -> (Tensor, Tensor)");
+  m.def("se_scale(Tensor x, Tensor s) -> Tensor");
+  m.def("se_bwd_reduce(Tensor g, Tensor x) -> Tensor");
+  m.def("se_gate_bwd(Tensor ds, Tensor s, Tensor h, Tensor w1, Tensor w2, int gate) -> (Tensor, Tensor, Tensor)");
+  m.def("se_bwd_dx(Tensor g, Tensor s, Tensor dp) -> Tensor");
+  m.def("se_wgrad(Tensor a, Tensor m, Tensor(a!) dw, bool want_bias) -> Tensor?");
   m.def("channel_reduce(Tensor? act, Tensor? grad, int mode) -> Tensor");
   m.def("column_accumulate(Tensor v, Tensor(a!) acc_sum, Tensor(b!)? acc_sq) -> ()");
   m.def("channel_fill_(Tensor(a!) x, Tensor idx, float value) -> ()");
@@ -611,5 +775,12 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("dwconv_wgrad", &dwconv_wgrad);
   m.impl("dwconv_act_fwd", &dwconv_act_fwd);
   m.impl("dwconv_act_dgrad", &dwconv_act_dgrad);
+  m.impl("se_pool", &se_pool);
+  m.impl("se_gate_fwd", &se_gate_fwd);
+  m.impl("se_scale", &se_scale);
+  m.impl("se_bwd_reduce", &se_bwd_reduce);
+  m.impl("se_gate_bwd", &se_gate_bwd);
+  m.impl("se_bwd_dx", &se_bwd_dx);
+  m.impl("se_wgrad", &se_wgrad);
   register_engine_ops_impl(m);
 }

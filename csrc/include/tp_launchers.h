@@ -61,6 +61,22 @@ int tp_dwconv_act_tay_slots(int H, int W, int C);
 hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
                                float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
                                int pad, int in_act, int out_act, hipStream_t st);
+// squeeze_excite.hip: out = x * s, s = gate(W2 . relu(W1 . mean_hw(x) + b1) + b2) on x (B, HW, C);
+// gate 0 Hardsigmoid, 1 Sigmoid; w1 (Cs, C), w2 (C, Cs) row-major; ws: splits * B * C floats when
+// splits = tp_se_splits(B, HW, C) > 1
+int tp_se_splits(int B, int HW, int C);
+hipError_t tp_se_pool(const float* x, float* p, float* ws, int splits, int B, int HW, int C, hipStream_t st);
+hipError_t tp_se_gate_fwd(const float* p, const float* w1, const float* b1, const float* w2, const float* b2,
+                          float* h, float* s, int B, int C, int Cs, int gate, hipStream_t st);
+hipError_t tp_se_scale(const float* x, const float* s, float* out, int B, int HW, int C, hipStream_t st);
+hipError_t tp_se_bwd_reduce(const float* g, const float* x, float* ds, float* ws, int splits, int B, int HW, int C,
+                            hipStream_t st);
+hipError_t tp_se_gate_bwd(const float* ds, const float* s, const float* h, const float* w1, const float* w2,
+                          float* dz2, float* dz1, float* dp, int B, int C, int Cs, int gate, hipStream_t st);
+hipError_t tp_se_bwd_dx(const float* g, const float* s, const float* dp, float* dx, int B, int HW, int C,
+                        hipStream_t st);
+hipError_t tp_se_wgrad(const float* a, const float* m, float* dw, float* db, int B, int R, int K, long long s0,
+                       long long s1, hipStream_t st);
 // conv_mfma.hip: nbatch independent GEMMs slab[i * splits + s] (M, N) = K range s of x[i] (M, K) . w[i] (N, K)^T
 int tp_conv_norm_splits(int splits, int K);
 hipError_t tp_conv_igemm_batched(const float* x, const float* w, int nbatch, int M, int K, int N, int cfg, int splits,

@@ -17,7 +17,7 @@ from .attributions import (
 )
 from .pruner import OptimizerPruner, Pruner
 from .utils import (find_best_module_for_attributions, get_mobilenet_pruning_graph, get_resnet_pruning_graph,
-                    get_vgg_pruning_graph)
+                    get_vgg_pruning_graph, is_channel_gate)
 
 __all__ = [
     "APoZAttributionMetric",
@@ -32,4 +32,5 @@ __all__ = [
     "get_mobilenet_pruning_graph",
     "get_resnet_pruning_graph",
     "get_vgg_pruning_graph",
+    "is_channel_gate",
 ]

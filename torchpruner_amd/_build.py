@@ -276,6 +276,30 @@ def build_dwconv_act_sanitizer(verbose: bool = False) -> Path:
     return exe
 
 
+def build_se_sanitizer(verbose: bool = False) -> Path:
+    """Build ``csrc/tests/se_validation.cpp`` against the squeeze-and-excitation launchers
+    (``squeeze_excite.hip``) with AddressSanitizer + UBSan on the HOST code only, like
+    :func:`build_dwconv_sanitizer`. Returns the executable path."""
+    out_dir = ROOT / "build" / "asan"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    headers = sorted((CSRC / "include").glob("*.h"))
+    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    src, obj = CSRC / "kernels" / "squeeze_excite.hip", out_dir / "squeeze_excite.o"
+    test_src, test_obj = CSRC / "tests" / "se_validation.cpp", out_dir / "se_validation.o"
+    jobs = []
+    if _needs_rebuild(src, obj, headers):
+        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
+                     "-c", src, "-o", obj])
+    if _needs_rebuild(test_src, test_obj, headers):
+        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
+    with ThreadPoolExecutor(max_workers=2) as ex:
+        list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / "se_validation"
+    if jobs or not exe.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
+    return exe
+
+
 def build_prefix_project_sanitizer(verbose: bool = False) -> Path:
     """Build ``csrc/tests/prefix_project_validation.cpp`` against the prefix-scan project-conv
     launcher (``prefix_project.hip``) with AddressSanitizer + UBSan on the HOST code only, like

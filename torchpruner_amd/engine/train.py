@@ -23,6 +23,11 @@ carried width from the expand conv through BN + ReLU6 (one fused apply pass, ``b
 the depthwise conv (float4 kernels at any pruned width) into the project conv, whose BN takes the
 shortcut in its apply pass; ``TORCHPRUNER_FUSE_RELU6=0`` keeps the unfused path.
 
+Squeeze-and-excitation gates (MobileNetV3, EfficientNet: :class:`_NativeSE`) run as three passes over
+the expanded activation forward (pool, scale: two reads, one write) and four backward (one read of
+g and x for the product-reduce, one read of g and one write for ``dx``), with both FCs of the gate in
+one launch each way; Hardswish stays an ATen op.
+
 Training-mode ``BatchNorm2d`` runs on deterministic NHWC batch-statistics / normalisation /
 backward kernels (K5, ``tpamd.bn_train_*``), training-mode ``nn.Dropout`` on a counter-based
 Philox kernel (K7b, mask regenerated in the backward), max-pool (argmax byte + gather backward)
@@ -50,6 +55,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..utils.graph import is_channel_gate
 from . import epochs
 from .fused_chain import _CU, CFG_SB, TUNER, WINO, WINO4S, WINO_LDS, _wino_splits, cpad, sk_candidates
 from .resnet_engine import wino4_cands
@@ -177,6 +183,10 @@ FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0, "bn_relu6": 0, "ir_b
 _NATIVE_DW = os.environ.get("TORCHPRUNER_NATIVE_DW", "1") != "0"
 # launches of the depthwise kernels (tests / diagnostics)
 DW_COUNTS = {"fwd": 0, "dgrad": 0, "wgrad": 0}
+# TORCHPRUNER_NATIVE_SE=0: squeeze-and-excitation gates stay on the library path (A/B switch, read once)
+_NATIVE_SE = os.environ.get("TORCHPRUNER_NATIVE_SE", "1") != "0"
+# gate forwards / backwards that ran on the squeeze_excite kernels (tests / diagnostics)
+SE_COUNTS = {"fwd": 0, "bwd": 0}
 
 
 class _BNLink:
@@ -1091,6 +1101,97 @@ def _native_dw_forward(self, x):
     return _NativeDWConv2d.apply(x, self.weight, self.bias, s, p)
 
 
+class _NativeSE(torch.autograd.Function):
+    """Squeeze-and-excitation gate ``x * gate(fc2(relu(fc1(mean_hw(x)))))`` on the NHWC kernels of
+    ``squeeze_excite.hip``: forward is a pool pass, one launch for both FCs and a scale pass;
+    backward one product-reduce pass over (g, x), one launch for the FC chain and one pass that
+    writes ``dx = g * s + dp / HW`` (the pool's broadcast gradient and the scale's gradient never
+    exist as tensors). The FC weights are read from the parameters in place ((Cs, C, 1, 1) of a
+    Conv2d and (Cs, C) of a Linear are the same bytes), their gradients are ordered sums written
+    in the parameters' shapes and strides, and are skipped for frozen parameters."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, gate):
+        T = ops.require()
+        xh = _nhwc(x)  # no copy for a channels_last input
+        w1c, w2c = w1.detach().contiguous(), w2.detach().contiguous()
+        p = T.se_pool(xh)
+        h, s = T.se_gate_fwd(p, w1c, b1.detach() if b1 is not None else None, w2c,
+                             b2.detach() if b2 is not None else None, gate)
+        out = T.se_scale(xh, s)
+        SE_COUNTS["fwd"] += 1
+        ctx.save_for_backward(xh, p, h, s, w1c, w2c)
+        ctx.meta = (gate, w1.stride(), w2.stride(), b1 is not None, b2 is not None)
+        return _as_nchw(out)
+
+    @staticmethod
+    def backward(ctx, gy):
+        T = ops.require()
+        xh, p, h, s, w1c, w2c = ctx.saved_tensors
+        gate, st1, st2, has_b1, has_b2 = ctx.meta
+        g = _nhwc(gy)
+        dz2, dz1, dp = T.se_gate_bwd(T.se_bwd_reduce(g, xh), s, h, w1c, w2c, gate)
+        SE_COUNTS["bwd"] += 1
+        dx = _as_nchw(T.se_bwd_dx(g, s, dp)) if ctx.needs_input_grad[0] else None
+        grads = []
+        for a, m, w, strides, need_w, need_b in ((dz1, p, w1c, st1, ctx.needs_input_grad[1],
+                                                  has_b1 and ctx.needs_input_grad[2]),
+                                                 (dz2, h, w2c, st2, ctx.needs_input_grad[3],
+                                                  has_b2 and ctx.needs_input_grad[4])):
+            dw = db = None
+            if need_w or need_b:
+                # dW in the parameter's exact strides (the _conv_wgrad contract: DDP bucket views)
+                dw = torch.empty_strided(tuple(w.shape), strides, dtype=torch.float32, device=g.device)
+                db = T.se_wgrad(a, m, dw, bool(need_b))
+                if not need_w:
+                    dw = None
+            grads += [dw, db]
+        return (dx, *grads, None)
+
+
+def _se_gate_code(m) -> int | None:
+    """The kernels' gate code of a channel gate with torchvision's ``SqueezeExcitation`` children (a
+    global ``avgpool``, a ReLU ``activation``, a Hardsigmoid / Sigmoid ``scale_activation``), else None."""
+    pool, act, gate = (getattr(m, n, None) for n in ("avgpool", "activation", "scale_activation"))
+    if not (type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1), [1, 1]) and type(act) is nn.ReLU):
+        return None
+    return 0 if type(gate) is nn.Hardsigmoid else 1 if type(gate) is nn.Sigmoid else None
+
+
+def se_eligible(m: nn.Module) -> bool:
+    """Channel gates (``utils.graph.is_channel_gate``) the native kernels compute: a global average
+    pool, fc1, ReLU, fc2 and a Hardsigmoid or Sigmoid gate (other inner activations, SiLU for one,
+    stay on the module's forward). Caveat: the test reads the children (torchvision's
+    ``SqueezeExcitation`` names and types), not the module's ``forward``; a module with exactly
+    these children that computes something else from them (a residual gate, a second use of the
+    pooled tensor) would be computed as ``x * s`` all the same. Exclude such a module by calling
+    :func:`disable_native_convs` on it, or with ``TORCHPRUNER_NATIVE_SE=0``."""
+    return is_channel_gate(m) and _se_gate_code(m) is not None
+
+
+def _se_fits(x: torch.Tensor, C: int, Cs: int) -> bool:
+    B, _, H, W = x.shape
+    cv = C // 4 if C % 4 == 0 else C
+    return (0 < B <= 65535 and H * W > 0 and x.numel() * 4 <= _MAX_BYTES and C + Cs <= ops.se.SE_MAX_FC
+            and B * -(-(H * W * cv) // 256) < (1 << 22) and B * max(C, Cs) < (1 << 24))
+
+
+def _native_se_forward(self, x):
+    """A channel gate's forward on :class:`_NativeSE`. None of the modules inside the gate is
+    called then, so the gate takes its own forward whenever one of them has a hook or global module
+    hooks exist, as for other dtypes / devices, tensors beyond 2 GiB and a gate whose structure
+    changed since it was switched; a hook on the gate module itself still fires."""
+    gate = _se_gate_code(self) if is_channel_gate(self) else None
+    if gate is None or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        return type(self).forward(self, x)
+    fc1, fc2 = self.fc1, self.fc2
+    (Cs, C), params = fc1.weight.shape[:2], (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    if x.shape[1] != C or fc2.weight.shape[1] != Cs or not _se_fits(x, C, Cs) or _hooked(self) \
+            or any(t is not None and (t.dtype != torch.float32 or t.device != x.device) for t in params):
+        return type(self).forward(self, x)
+    return _NativeSE.apply(x, *params, gate)
+
+
 def _ir_unit(u) -> bool:
     return (type(u) is nn.Sequential and len(u) == 3 and isinstance(u[0], nn.Conv2d)
             and isinstance(u[1], nn.BatchNorm2d) and type(u[2]) in (nn.ReLU6, nn.ReLU))
@@ -1268,6 +1369,10 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
     other ``nn.Sequential`` fuse like ``(BatchNorm2d, ReLU)`` ones. ``TORCHPRUNER_FUSE_RELU6=0``
     turns the ReLU6 fusions and the block forward off. Also switched: depthwise convs
     (:func:`dw_eligible`, the NHWC stencil kernels; ``TORCHPRUNER_NATIVE_DW=0`` leaves them on the
+    library path), squeeze-and-excitation gates (:func:`se_eligible`, train and eval mode, with or
+    without ``fuse``: pool, both FCs, gate and scale on the ``squeeze_excite`` kernels; the modules
+    inside the gate are not called then, so a gate with a hook on one of them takes its own forward,
+    while a hook on the gate itself still fires; ``TORCHPRUNER_NATIVE_SE=0`` leaves gates on the
     library path), ``nn.Linear`` (MFMA GEMM), ``nn.MaxPool2d``,
     ``nn.AdaptiveAvgPool2d`` and, with ``dropout``, training-mode ``nn.Dropout`` (Philox masks
     seeded from torch's CPU RNG: a different random stream than PyTorch's dropout). Returns the
@@ -1289,6 +1394,11 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
             m.forward = types.MethodType(_native_ir_forward, m)
             switched.append(m)
             inner.update(id(c) for c in m.conv.modules() if type(c) is nn.Sequential)
+        elif _NATIVE_SE and se_eligible(m):
+            # (its pool and fcs are switched further down like any other leaf: the gate's fallback
+            # forward still runs them on the native kernels)
+            m.forward = types.MethodType(_native_se_forward, m)
+            switched.append(m)
         elif bn and fuse and _block_kind(m) is not None:
             m.forward = types.MethodType(_native_block_forward, m)
             switched.append(m)

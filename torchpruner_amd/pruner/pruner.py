@@ -16,6 +16,12 @@ Differences (deliberate fixes):
   accepted as a cascading module (its channel c goes with channel c of its producer), every other
   grouped convolution is rejected explicitly, and a cascade is validated before anything is
   sliced; transposed convolutions are pruned on their correct weight axes;
+* a channel gate (``utils.graph.is_channel_gate``: a squeeze-and-excitation module) is accepted
+  as a cascading module: the probe passes its input through (it would otherwise spread one NaN
+  channel over all of them), and cutting it along ``"in"`` cuts ``fc1``'s input columns and
+  ``fc2``'s output rows and bias; a dense cascading module whose whole input turns NaN while only
+  some of the pruned module's outputs were nanified (an unlisted channel-mixing module upstream)
+  is rejected instead of being cut to width 0;
 * in a live process group the pruning indices are broadcast from rank 0 (R5) so every
   data-parallel replica prunes identically.
 """
@@ -33,6 +39,7 @@ from torch.nn.modules.conv import _ConvNd, _ConvTransposeNd
 from torch.nn.modules.dropout import _DropoutNd
 
 from .. import ops
+from ..utils.graph import is_channel_gate
 from ..utils.profiling import trace_range
 from ..parallel import dist as pdist
 from .opt_pruner import OptimizerPruner
@@ -75,6 +82,7 @@ class Pruner:
         # What the probe finds lives in a per-call context, not on the modules (the
         # reference stashes _nan_indices / _activation_len on them, pruner.py:155-167, which is
         # not reentrant: two pruners probing one module would overwrite each other's findings)
+        _check_gate_listing(cascading_modules)
         probe = _ProbeRun()
         handles = [module.register_forward_hook(self._nanify_hook(indices))]
         for next_module in cascading_modules:
@@ -84,6 +92,7 @@ class Pruner:
         finally:
             for h in handles:
                 h.remove()
+        _check_not_mixed(module, indices, cascading_modules, probe)
 
         # 2. Prune every cascading module whose input saw NaNs (inputs), then the module (outputs).
         # Every cut is validated before the first one is made: a rejected cascade (an unsupported
@@ -107,7 +116,14 @@ class Pruner:
         indices = _as_index_array(indices)
         logger.info("Pruning %d units from %s (%s)", len(indices), module, direction)
         transposed = isinstance(module, _ConvTransposeNd)
-        if _is_depthwise(module):
+        if is_channel_gate(module):
+            # out = in * gate(pool(in)): channel c is one input column of fc1 and one output row
+            # (and bias entry) of fc2
+            self.prune_parameter(module.fc1, "weight", indices, axis=1)
+            self.prune_parameters(module.fc2, ["weight", "bias"], indices, axis=0)
+            _set_width(module.fc1, "in", module.fc1.weight.shape[1])
+            _set_width(module.fc2, "out", module.fc2.weight.shape[0])
+        elif _is_depthwise(module):
             # a per-channel pass-through: channel c is one (1, k, k) filter and one bias entry; the
             # module stays depthwise at the new width
             self.prune_parameters(module, ["weight", "bias"], indices, axis=0)
@@ -228,6 +244,9 @@ class Pruner:
 
         def _hook(module, input, __):
             x = input[0]
+            # a channel gate mixes every channel into every factor: the probe sees it as the
+            # per-channel pass-through it is for pruning (its input comes back as its output)
+            passed = x if is_channel_gate(module) else None
             if probe is not None:
                 probe.activation_len[module] = float(x.shape[1])
             else:
@@ -245,6 +264,7 @@ class Pruner:
                     probe.nan_indices[module] = indices
                 else:
                     setattr(module, "_nan_indices", indices)
+            return passed
 
         return _hook
 
@@ -287,6 +307,12 @@ def _check_prunable(module, direction):
     """Raise unless ``module`` can be cut along ``direction`` (called for every module of a
     cascade before anything is sliced)."""
     assert direction in ["out", "in"], "direction should be 'out' or 'in'"
+    if is_channel_gate(module):
+        if direction == "out":
+            raise NotImplementedError("a channel gate's outputs are tied one-to-one to its inputs: prune the layer "
+                                      "that produces its input and list the gate among that layer's cascading "
+                                      "modules")
+        return
     if direction == "out":
         assert any(isinstance(module, t) for t in SUPPORTED_OUT_PRUNING_MODULES), \
             f"Cannot prune outgoing activations on this module. Only the following are supported " \
@@ -303,6 +329,40 @@ def _check_prunable(module, direction):
             raise NotImplementedError("a depthwise convolution's outputs are tied one-to-one to its inputs: prune "
                                       "the layer that produces its input and list the depthwise convolution among "
                                       "that layer's cascading modules")
+
+
+def _check_gate_listing(cascading_modules):
+    """A gate is cut as a whole: listing one of its inner modules beside it would cut that module
+    twice (and the probe never shows the inner modules the pruned channels)."""
+    for gate in cascading_modules:
+        if not is_channel_gate(gate):
+            continue
+        inner = {id(c) for c in gate.modules() if c is not gate}
+        for m in cascading_modules:
+            if id(m) in inner:
+                raise ValueError(f"{type(m).__name__} is a module inside the channel gate {type(gate).__name__} that "
+                                 "the same cascade lists: list the gate alone")
+
+
+def _check_not_mixed(module, indices, cascading_modules, probe):
+    """Raise when a dense cascading module saw NaN in every input channel although fewer than all
+    of ``module``'s outputs were nanified: a channel-mixing module (an unlisted gate, for one)
+    sits between the two, and cutting would leave a weight of width 0."""
+    weight = getattr(module, "weight", None)
+    if weight is None or not isinstance(module, (nn.Linear, _ConvNd)):
+        return
+    n_out = weight.shape[1 if isinstance(module, _ConvTransposeNd) else 0]
+    if len(indices) >= n_out:
+        return  # pruning every output stays allowed
+    for m in cascading_modules:
+        idx = probe.nan_indices.get(m)
+        if idx is None or not isinstance(m, (nn.Linear, _ConvNd)) or _is_depthwise(m):
+            continue
+        if len(idx) >= probe.activation_len[m]:
+            raise ValueError(f"every input channel of the cascading module {m} depends on the {len(indices)} of "
+                             f"{n_out} pruned outputs: a module that mixes channels (a squeeze-and-excitation gate, "
+                             "for one) lies upstream of it and is not listed; list the gate itself among the "
+                             "cascading modules")
 
 
 def _set_width(module, direction, n):

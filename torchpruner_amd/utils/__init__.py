@@ -5,6 +5,7 @@ from .graph import (
     get_mobilenet_pruning_graph,
     get_resnet_pruning_graph,
     get_vgg_pruning_graph,
+    is_channel_gate,
 )
 from .flops import count_parameters, count_flops
 from .train import recalibrate_bn, test, train
@@ -16,6 +17,7 @@ __all__ = [
     "get_mobilenet_pruning_graph",
     "get_resnet_pruning_graph",
     "get_vgg_pruning_graph",
+    "is_channel_gate",
     "count_parameters",
     "count_flops",
     "train",
