@@ -62,7 +62,12 @@ at::Tensor channel_reduce(const c10::optional<at::Tensor>& act, const c10::optio
   TORCH_CHECK(!need_g || grad.has_value(), "mode ", mode, " needs the gradient");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(ref.device());
   auto out = at::empty({s.B, s.C}, ref.options());
+  if (out.numel() == 0) return out;
+  const int64_t lim = int64_t(1) << 31;
+  TORCH_CHECK(s.B < lim && s.C < lim && s.S > 0 && s.S < lim, "channel_reduce: empty or oversized (B, C, S)");
+  if (act.has_value() && grad.has_value()) TORCH_CHECK(act->device() == grad->device(), "act/grad device mismatch");
   const int wse = tp_channel_reduce_ws_elems((int)s.B, (int)s.C, (int)s.S, s.cl ? 1 : 0);
+  TORCH_CHECK(wse >= 0, "channel_reduce: workspace of 2^31 elements or more");
   at::Tensor ws;
   if (wse > 0) ws = at::empty({wse}, ref.options());
   TP_CHECK_HIP(tp_channel_reduce(need_a ? act->data_ptr<float>() : nullptr,
@@ -75,14 +80,17 @@ at::Tensor channel_reduce(const c10::optional<at::Tensor>& act, const c10::optio
 void column_accumulate(const at::Tensor& v, at::Tensor& acc_sum, const c10::optional<at::Tensor>& acc_sq) {
   check_cuda_f32(v, "v");
   TORCH_CHECK(v.dim() == 2 && v.is_contiguous(), "v must be contiguous (B, C)");
-  TORCH_CHECK(acc_sum.scalar_type() == at::kDouble && acc_sum.numel() == v.size(1) && acc_sum.is_contiguous(),
-              "acc_sum must be a contiguous float64 (C,) tensor");
+  TORCH_CHECK(acc_sum.device() == v.device() && acc_sum.scalar_type() == at::kDouble &&
+                  acc_sum.numel() == v.size(1) && acc_sum.is_contiguous(),
+              "acc_sum must be a contiguous float64 (C,) tensor on v's device");
   double* sq = nullptr;
   if (acc_sq.has_value()) {
-    TORCH_CHECK(acc_sq->scalar_type() == at::kDouble && acc_sq->numel() == v.size(1) && acc_sq->is_contiguous(),
-                "acc_sq must be a contiguous float64 (C,) tensor");
+    TORCH_CHECK(acc_sq->device() == v.device() && acc_sq->scalar_type() == at::kDouble &&
+                    acc_sq->numel() == v.size(1) && acc_sq->is_contiguous(),
+                "acc_sq must be a contiguous float64 (C,) tensor on v's device");
     sq = acc_sq->data_ptr<double>();
   }
+  if (v.numel() == 0) return;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
   TP_CHECK_HIP(tp_column_accumulate(v.data_ptr<float>(), acc_sum.data_ptr<double>(), sq, (int)v.size(0),
                                     (int)v.size(1), cur_stream()));
@@ -101,6 +109,7 @@ void score_fold_(at::TensorList T, at::TensorList acc, bool take_abs, int64_t af
   auto flush = [&]() {
     if (tp.empty()) return;
     const int n_ws = tp_score_fold_ws_elems(bs.data(), cs.data(), (int)tp.size());
+    TORCH_CHECK(n_ws >= 0, "score_fold_: empty slab or a workspace of 2^31 elements or more");
     at::Tensor ws = at::empty({std::max(n_ws, 1)}, T[0].options().dtype(at::kDouble));
     TP_CHECK_HIP(tp_score_fold_multi(tp.data(), ap.data(), bs.data(), cs.data(), rs.data(), (int)tp.size(),
                                      take_abs ? 1 : 0, (int)after, ws.data_ptr<double>(), cur_stream()));
@@ -108,13 +117,15 @@ void score_fold_(at::TensorList T, at::TensorList acc, bool take_abs, int64_t af
   };
   for (size_t i = 0; i < T.size(); ++i) {
     check_cuda_f32(T[i], "T");
+    TORCH_CHECK(T[i].device() == T[0].device(), "score tensors must share a device");
     TORCH_CHECK((T[i].dim() == 2 || T[i].dim() == 3) && T[i].is_contiguous(),
                 "T must be contiguous (B, C) or (R, B, C) partial slots");
     const int64_t nb = T[i].size(-2), nc = T[i].size(-1), nr = T[i].dim() == 3 ? T[i].size(0) : 1;
     double* a = nullptr;
     if (acc[i].defined() && acc[i].numel() > 0) {
-      TORCH_CHECK(acc[i].scalar_type() == at::kDouble && acc[i].is_contiguous() && acc[i].numel() == nc,
-                  "acc must be a contiguous float64 (C,) tensor");
+      TORCH_CHECK(acc[i].device() == T[i].device() && acc[i].scalar_type() == at::kDouble &&
+                      acc[i].is_contiguous() && acc[i].numel() == nc,
+                  "acc must be a contiguous float64 (C,) tensor on T's device");
       a = acc[i].data_ptr<double>();
     }
     tp.push_back(T[i].data_ptr<float>());
@@ -130,8 +141,10 @@ void score_fold_(at::TensorList T, at::TensorList acc, bool take_abs, int64_t af
 void channel_fill_(at::Tensor& x, const at::Tensor& idx, double value) {
   check_cuda_f32(x, "x");
   TORCH_CHECK(x.is_contiguous(), "channel_fill_ needs a contiguous NC* tensor");
-  TORCH_CHECK(idx.scalar_type() == at::kLong && idx.is_cuda() && idx.dim() == 1, "idx must be int64 (n,) on GPU");
+  TORCH_CHECK(idx.scalar_type() == at::kLong && idx.device() == x.device() && idx.dim() == 1,
+              "idx must be int64 (n,) on x's device");
   BCS s = bcs_of(x);
+  if (x.numel() == 0 || idx.numel() == 0) return;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto ic = idx.contiguous();
   TP_CHECK_HIP(tp_channel_fill(x.data_ptr<float>(), s.B, (int)s.C, s.S, ic.data_ptr<int64_t>(), (int)ic.numel(),
@@ -143,6 +156,7 @@ at::Tensor nan_channels(const at::Tensor& x_) {
   auto x = x_.contiguous();
   BCS s = bcs_of(x);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  if (x.numel() == 0) return at::zeros({s.C}, x.options().dtype(at::kByte));
   auto flags = at::empty({s.C}, x.options().dtype(at::kByte));
   TP_CHECK_HIP(tp_nan_channels(x.data_ptr<float>(), s.B, (int)s.C, s.S, flags.data_ptr<uint8_t>(), cur_stream()));
   return flags;
@@ -160,7 +174,8 @@ std::vector<at::Tensor> gather_multi(at::TensorList srcs, at::IntArrayRef axes, 
   // Group tensors with equal element size into launches of up to 8 descriptors.
   std::vector<at::Tensor> csrc;
   for (size_t i = 0; i < srcs.size(); ++i) {
-    TORCH_CHECK(srcs[i].is_cuda(), "gather_multi inputs must be GPU tensors");
+    TORCH_CHECK(srcs[i].is_cuda() && srcs[i].device() == srcs[0].device(),
+                "gather_multi inputs must be GPU tensors on one device");
     auto c = srcs[i].contiguous();
     int64_t ax = axes[i] < 0 ? axes[i] + c.dim() : axes[i];
     TORCH_CHECK(ax >= 0 && ax < c.dim(), "bad axis");
@@ -180,7 +195,7 @@ std::vector<at::Tensor> gather_multi(at::TensorList srcs, at::IntArrayRef axes, 
       s.clear(); d.clear(); outer.clear(); n.clear(); inner.clear();
     };
     for (size_t i = 0; i < csrc.size(); ++i) {
-      if ((int)csrc[i].element_size() != es) continue;
+      if ((int)csrc[i].element_size() != es || outs[i].numel() == 0) continue;
       const auto& c = csrc[i];
       int64_t ax = axes[i] < 0 ? axes[i] + c.dim() : axes[i];
       long long o = 1, in = 1;
@@ -200,15 +215,18 @@ std::vector<at::Tensor> gather_multi(at::TensorList srcs, at::IntArrayRef axes, 
 
 at::Tensor prefix_mask(const at::Tensor& z, const at::Tensor& rank, int64_t p0, int64_t K) {
   check_cuda_f32(z, "z");
-  TORCH_CHECK(rank.scalar_type() == at::kInt && rank.is_cuda() && rank.dim() == 1 && rank.is_contiguous(),
-              "rank must be a contiguous int32 (C,) GPU tensor");
+  TORCH_CHECK(rank.scalar_type() == at::kInt && rank.device() == z.device() && rank.dim() == 1 && rank.is_contiguous(),
+              "rank must be a contiguous int32 (C,) tensor on z's device");
   BCS s = bcs_of(z);
   TORCH_CHECK(rank.numel() == s.C, "rank length must equal channel count");
+  TORCH_CHECK(p0 >= 0 && K >= 0 && p0 + K < (int64_t(1) << 31) && s.C < (int64_t(1) << 31) && s.S < (int64_t(1) << 31),
+              "bad prefix range (p0 ", p0, ", K ", K, ")");
   auto sz = z.sizes().vec();
   sz[0] = sz[0] * K;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
   auto out = at::empty(sz, z.options().memory_format(s.cl ? at::MemoryFormat::ChannelsLast
                                                             : at::MemoryFormat::Contiguous));
+  if (out.numel() == 0) return out;
   TP_CHECK_HIP(tp_prefix_mask(z.data_ptr<float>(), out.data_ptr<float>(), rank.data_ptr<int>(), z.numel(), (int)s.C,
                               (int)s.S, s.cl ? 1 : 0, (int)p0, (int)K, cur_stream()));
   return out;
@@ -251,10 +269,16 @@ void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv
                      double scale) {
   check_cuda_f32(L, "losses");
   TORCH_CHECK(L.dim() == 2 && L.is_contiguous(), "losses must be contiguous (K+1, B)");
-  TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous(), "perm must be int32");
-  TORCH_CHECK(sv.scalar_type() == at::kDouble && sv.dim() == 2 && sv.is_contiguous(), "sv must be float64 (d, n)");
+  TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous() && perm.device() == L.device(),
+              "perm must be int32 on the losses' device");
+  TORCH_CHECK(sv.scalar_type() == at::kDouble && sv.dim() == 2 && sv.is_contiguous() && sv.device() == L.device(),
+              "sv must be float64 (d, n) on the losses' device");
   const int64_t K = L.size(0) - 1, B = L.size(1);
-  TORCH_CHECK(row0 + B <= sv.size(0) && k0 + K <= perm.numel() && perm.numel() == sv.size(1), "shape mismatch");
+  TORCH_CHECK(K >= 0 && row0 >= 0 && k0 >= 0 && row0 + B <= sv.size(0) && k0 + K <= perm.numel() &&
+                  perm.numel() == sv.size(1), "shape mismatch");
+  TORCH_CHECK(L.numel() < (int64_t(1) << 31) && sv.size(0) < (int64_t(1) << 31) && sv.size(1) < (int64_t(1) << 31),
+              "shapley_scatter operands must stay below 2^31 elements per dimension");
+  if (K == 0 || B == 0) return;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(L.device());
   TP_CHECK_HIP(tp_shapley_scatter(L.data_ptr<float>(), perm.data_ptr<int>(), sv.data_ptr<double>(), (int)row0,
                                   (int)B, (int)sv.size(1), (int)k0, (int)K, scale, cur_stream()));
@@ -263,10 +287,15 @@ void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv
 void shapley_column(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv_col, int64_t k0, double scale) {
   check_cuda_f32(L, "losses");
   TORCH_CHECK(L.dim() == 2 && L.is_contiguous(), "losses must be contiguous (K+1, B)");
-  TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous(), "perm must be int32");
-  TORCH_CHECK(sv_col.scalar_type() == at::kDouble && sv_col.is_contiguous(), "sv_col must be float64 (n,)");
+  TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous() && perm.device() == L.device(),
+              "perm must be int32 on the losses' device");
+  TORCH_CHECK(sv_col.scalar_type() == at::kDouble && sv_col.is_contiguous() && sv_col.device() == L.device(),
+              "sv_col must be float64 (n,) on the losses' device");
   const int64_t K = L.size(0) - 1;
-  TORCH_CHECK(k0 + K <= perm.numel() && perm.numel() == sv_col.numel(), "shape mismatch");
+  TORCH_CHECK(K >= 0 && k0 >= 0 && k0 + K <= perm.numel() && perm.numel() == sv_col.numel(), "shape mismatch");
+  TORCH_CHECK(L.numel() < (int64_t(1) << 31) && perm.numel() < (int64_t(1) << 31),
+              "shapley_column operands must stay below 2^31 elements");
+  if (K == 0 || L.size(1) == 0) return;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(L.device());
   TP_CHECK_HIP(tp_shapley_column(L.data_ptr<float>(), perm.data_ptr<int>(), sv_col.data_ptr<double>(),
                                  (int)L.size(1), (int)k0, (int)K, scale, cur_stream()));
@@ -277,11 +306,14 @@ std::tuple<at::Tensor, at::Tensor> cross_entropy(const at::Tensor& logits_, cons
   check_cuda_f32(logits_, "logits");
   TORCH_CHECK(logits_.dim() == 2, "logits must be (B, classes)");
   auto logits = logits_.contiguous();
+  TORCH_CHECK(target_.device() == logits_.device(), "target must be on the logits' device");
   auto target = target_.to(at::kLong).contiguous();
   TORCH_CHECK(target.numel() == logits.size(0), "target length mismatch");
+  TORCH_CHECK(logits.size(1) > 0 && logits.size(1) < (int64_t(1) << 31), "logits need at least one class");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
   auto loss = at::empty({logits.size(0)}, logits.options());
   at::Tensor grad = want_grad ? at::empty_like(logits) : at::Tensor();
+  if (logits.size(0) == 0) return {loss, grad};
   TP_CHECK_HIP(tp_cross_entropy(logits.data_ptr<float>(), target.data_ptr<int64_t>(), loss.data_ptr<float>(),
                                 want_grad ? grad.data_ptr<float>() : nullptr, (int)logits.size(0),
                                 (int)logits.size(1), (float)gscale, cur_stream()));
@@ -310,7 +342,10 @@ at::Tensor augment_u8(const at::Tensor& src, const at::Tensor& idx, const c10::o
               "mean / inv_std must have C elements");
   TORCH_CHECK(pad >= 0, "pad must be >= 0");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+  TORCH_CHECK(idx.device() == src.device() && mean.device() == src.device() && inv_std.device() == src.device() &&
+                  (!ap || aug->device() == src.device()), "augment_u8 operands must share a device");
   auto out = at::empty({B, C, H, W}, src.options().dtype(at::kFloat));
+  if (out.numel() == 0) return out;
   TP_CHECK_HIP(tp_augment_u8(src.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), ap, (int)B, (int)C, (int)H, (int)W,
                              (int)pad, mean.data_ptr<float>(), inv_std.data_ptr<float>(), out.data_ptr<float>(),
                              cur_stream()));
@@ -323,7 +358,11 @@ at::Tensor dropout(const at::Tensor& x_, int64_t seed, double p) {
   auto x = x_.contiguous();
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  auto y = at::empty_like(x);
+  // the kernel loads float4: a contiguous view into the middle of a storage (x[1:] of an odd-width
+  // matrix) is copied to storage of its own; the mask depends on the element index only
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone(at::MemoryFormat::Contiguous);
+  auto y = at::empty(x.sizes(), x.options());
+  if (x.numel() == 0) return y;
   TP_CHECK_HIP(tp_dropout(x.data_ptr<float>(), y.data_ptr<float>(), x.numel(), (unsigned long long)seed, p,
                           cur_stream()));
   return y;

@@ -7,7 +7,8 @@ extern "C" {
 // channel_reduce.hip
 hipError_t tp_channel_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C, int S,
                              int mode, int channels_last, hipStream_t st);
-int tp_channel_reduce_ws_elems(int B, int C, int S, int channels_last);
+int tp_channel_reduce_ws_elems(int B, int C, int S, int channels_last);  // -1: bad sizes / 2^31 elements and more
+int tp_channel_reduce_chunks(int B, int C, int S, int vec);
 hipError_t tp_column_accumulate(const float* v, double* acc_sum, double* acc_sq, int B, int C, hipStream_t st);
 // prune_ops.hip
 hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx, int nidx, float value,
@@ -30,6 +31,7 @@ hipError_t tp_cross_entropy(const float* logits, const int64_t* target, float* l
 hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt, const int* perm,
                              float* out, int N, int C, int Co, int n, int p0, int cnt, hipStream_t st);
 // train_ops.hip
+void tp_philox4x32(unsigned long long ctr, unsigned long long key, unsigned* out);  // host: the dropout generator
 hipError_t tp_dropout(const float* x, float* y, long long n, unsigned long long seed, double p, hipStream_t st);
 hipError_t tp_maxpool_fwd_arg(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, int k, int s, int pad,
                               hipStream_t st);

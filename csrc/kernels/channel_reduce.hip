@@ -188,12 +188,15 @@ __global__ __launch_bounds__(256) void nhwc_finish(const float* __restrict__ ws,
   out[t] = finish<MODE>(v);
 }
 
+// spatial chunks of the NHWC launch on the float4 (vec) or the scalar kernel
+inline int reduce_chunks(int B, int C, int S, bool vec) { return vec ? nhwc_v4_chunks(B, C, S) : nhwc_chunks(S); }
+
 template <int MODE>
 static hipError_t launch_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C, int S,
                                 int channels_last, hipStream_t st) {
   const bool al = ((((uintptr_t)act) | ((uintptr_t)grad)) % 16) == 0;
   if (channels_last && C % 32 == 0 && al) {
-    const int chunks = ws ? nhwc_v4_chunks(B, C, S) : 1;
+    const int chunks = ws ? reduce_chunks(B, C, S, true) : 1;
     const int chunk = (S + chunks - 1) / chunks;
     const int Q = C / 4, qb = nhwc_v4_qb(C);
     dim3 grid(ceil_div(Q, qb), B, chunks);
@@ -203,7 +206,7 @@ static hipError_t launch_reduce(const float* act, const float* grad, float* out,
     return hipGetLastError();
   }
   if (channels_last) {
-    const int chunks = ws ? nhwc_chunks(S) : 1;
+    const int chunks = ws ? reduce_chunks(B, C, S, false) : 1;
     const int chunk = (S + chunks - 1) / chunks;
     dim3 grid(ceil_div(C, 64), B, chunks);
     channel_reduce_nhwc<MODE><<<grid, 256, 0, st>>>(act, grad, out, ws, C, S, chunk);
@@ -215,6 +218,7 @@ static hipError_t launch_reduce(const float* act, const float* grad, float* out,
   const int Se = vec ? S / 4 : S;
   int lpr = Se >= 64 ? 64 : (Se >= 16 ? 16 : (Se >= 4 ? 4 : 1));
   long long threads = rows * lpr;
+  if (threads / 256 >= (1ll << 31) - 1) return hipErrorInvalidValue;
   unsigned grid = ceil_div(threads, 256);
 #define TP_L(L)                                                                           \
   if (lpr == L) {                                                                         \
@@ -280,7 +284,7 @@ __global__ __launch_bounds__(1024) void score_fold_rows(ScoreBatch batch, int ta
   const int r0 = blockIdx.z * FOLD_ROWS;
   if (c_base >= s.C || r0 >= s.B) return;  // uniform per block
   const int r1 = min(s.B, r0 + FOLD_ROWS);
-  const bool vec = (s.C & 3) == 0;
+  const bool vec = (s.C & 3) == 0 && (reinterpret_cast<uintptr_t>(s.T) & 15) == 0;  // float4 rows
   const int cols = min(256, s.C - c_base);
   const int nq = vec ? (cols + 3) / 4 : min(cols, 256);
   const int RG = min(1024 / nq, FOLD_ROWS);
@@ -354,24 +358,32 @@ __global__ __launch_bounds__(256) void score_fold_final(ScoreBatch batch, const 
 
 }  // namespace tp
 
+// doubles of workspace for one tp_score_fold_multi call; -1 for bad sizes or 2^31 elements and more
 extern "C" int tp_score_fold_ws_elems(const int* B, const int* C, int count) {
+  if (!B || !C || count <= 0 || count > 16) return -1;
   int maxc = 0, maxb = 0;
   for (int i = 0; i < count; ++i) {
+    if (B[i] <= 0 || C[i] <= 0) return -1;
     maxc = std::max(maxc, C[i]);
     maxb = std::max(maxb, B[i]);
   }
-  return count * tp::ceil_div(maxb, tp::FOLD_ROWS) * maxc;
+  const long long n = (long long)count * tp::ceil_div(maxb, tp::FOLD_ROWS) * maxc;
+  return n < (1ll << 31) ? (int)n : -1;
 }
 
 // ws: tp_score_fold_ws_elems doubles
 extern "C" hipError_t tp_score_fold_multi(float* const* T, double* const* acc, const int* B, const int* C,
                                           const int* R, int count, int take_abs, int after, double* ws,
                                           hipStream_t st) {
-  if (count <= 0 || count > 16) return hipErrorInvalidValue;
+  if (count <= 0 || count > 16 || !T || !acc || !B || !C || !R || after < 0 || after > 2) return hipErrorInvalidValue;
+  if (tp_score_fold_ws_elems(B, C, count) < 0) return hipErrorInvalidValue;
   tp::ScoreBatch b{};
   int maxc = 0, maxb = 0;
   bool any_acc = false;
   for (int i = 0; i < count; ++i) {
+    // (the kernels index a slab with 64-bit offsets; the slot count only has to be positive)
+    if (!T[i] || R[i] <= 0 || (reinterpret_cast<uintptr_t>(T[i]) & 3) || (reinterpret_cast<uintptr_t>(acc[i]) & 7))
+      return hipErrorInvalidValue;
     b.d[i] = tp::ScoreDesc{T[i], acc[i], B[i], C[i], R[i]};
     maxc = std::max(maxc, C[i]);
     maxb = std::max(maxb, B[i]);
@@ -379,6 +391,7 @@ extern "C" hipError_t tp_score_fold_multi(float* const* T, double* const* acc, c
   }
   if (any_acc && !ws) return hipErrorInvalidValue;
   const int nr = tp::ceil_div(maxb, tp::FOLD_ROWS);
+  if (nr > 65535) return hipErrorInvalidValue;  // grid.z
   tp::score_fold_rows<<<dim3(tp::ceil_div(maxc, 256), count, nr), 1024, 0, st>>>(b, take_abs, after, ws, maxc, nr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !any_acc) return e;
@@ -386,15 +399,33 @@ extern "C" hipError_t tp_score_fold_multi(float* const* T, double* const* acc, c
   return hipGetLastError();
 }
 
+// spatial chunks of the channels_last launch on the float4 (vec: C % 32 == 0, 16-byte aligned
+// operands) or the scalar kernel when a workspace is given; 0 for bad sizes
+extern "C" int tp_channel_reduce_chunks(int B, int C, int S, int vec) {
+  if (B <= 0 || C <= 0 || S <= 0 || (vec && C % 32 != 0)) return 0;
+  return tp::reduce_chunks(B, C, S, vec != 0);
+}
+
+// floats of workspace (0: none needed); -1 for bad sizes or 2^31 elements and more
 extern "C" int tp_channel_reduce_ws_elems(int B, int C, int S, int channels_last) {
-  int k = channels_last ? tp::nhwc_chunks(S) : 1;
-  if (channels_last && C % 32 == 0) k = std::max(k, tp::nhwc_v4_chunks(B, C, S));  // either kernel may run
-  return k > 1 ? B * C * k : 0;
+  if (B <= 0 || C <= 0 || S <= 0) return -1;
+  int k = channels_last ? tp::reduce_chunks(B, C, S, false) : 1;
+  if (channels_last && C % 32 == 0) k = std::max(k, tp::reduce_chunks(B, C, S, true));  // either kernel may run
+  if ((long long)B * C >= (1ll << 31)) return -1;
+  const long long n = (long long)B * C * k;
+  if (n >= (1ll << 31)) return -1;
+  return k > 1 ? (int)n : 0;
 }
 
 extern "C" hipError_t tp_channel_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C,
                                         int S, int mode, int channels_last, hipStream_t st) {
   using namespace tp;
+  if (mode < TAYLOR_ABS || mode > SUM_GRAD || B <= 0 || C <= 0 || S <= 0 || !out) return hipErrorInvalidValue;
+  const bool need_a = mode == TAYLOR_ABS || mode == TAYLOR_SIGNED || mode == APOZ_POS, need_g = mode != APOZ_POS;
+  if ((need_a && !act) || (need_g && !grad)) return hipErrorInvalidValue;
+  if (((uintptr_t)act | (uintptr_t)grad | (uintptr_t)out | (uintptr_t)ws) & 3) return hipErrorInvalidValue;
+  if (channels_last && B > 65535) return hipErrorInvalidValue;                    // grid.y = B
+  if (tp_channel_reduce_ws_elems(B, C, S, channels_last) < 0) return hipErrorInvalidValue;  // (B, C, chunks) past 2^31
   switch (mode) {
     case TAYLOR_ABS: return launch_reduce<TAYLOR_ABS>(act, grad, out, ws, B, C, S, channels_last, st);
     case TAYLOR_SIGNED: return launch_reduce<TAYLOR_SIGNED>(act, grad, out, ws, B, C, S, channels_last, st);
@@ -407,6 +438,7 @@ extern "C" hipError_t tp_channel_reduce(const float* act, const float* grad, flo
 
 extern "C" hipError_t tp_column_accumulate(const float* v, double* acc_sum, double* acc_sq, int B, int C,
                                            hipStream_t st) {
+  if (!v || !acc_sum || B <= 0 || C <= 0) return hipErrorInvalidValue;
   tp::column_accumulate<<<tp::ceil_div(C, 64), 256, 0, st>>>(v, acc_sum, acc_sq, B, C);
   return hipGetLastError();
 }

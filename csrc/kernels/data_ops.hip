@@ -44,8 +44,9 @@ __global__ __launch_bounds__(256) void augment_u8(const uint8_t* __restrict__ sr
 
 extern "C" hipError_t tp_augment_u8(const uint8_t* src, const int64_t* idx, const int* aug, int B, int C, int H, int W,
                                     int pad, const float* mean, const float* inv_std, float* out, hipStream_t st) {
-  if (B <= 0) return hipSuccess;
-  if (pad < 0 || C <= 0 || H <= 0 || W <= 0) return hipErrorInvalidValue;
+  if (!src || !idx || !mean || !inv_std || !out) return hipErrorInvalidValue;
+  if (B <= 0 || pad < 0 || C <= 0 || H <= 0 || W <= 0 || (double)B * C * H * W >= 9.0e18) return hipErrorInvalidValue;
+  if (((uintptr_t)aug | (uintptr_t)mean | (uintptr_t)inv_std | (uintptr_t)out) & 3) return hipErrorInvalidValue;
   const long long total = (long long)B * C * H * W;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
   tp::augment_u8<<<grid, 256, 0, st>>>(src, idx, aug, B, C, H, W, pad, mean, inv_std, out);

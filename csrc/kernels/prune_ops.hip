@@ -72,8 +72,10 @@ __global__ __launch_bounds__(256) void gather_multi(GatherBatch batch, const int
 
 extern "C" hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx,
                                       int nidx, float value, hipStream_t st) {
+  if (!x || B <= 0 || C <= 0 || S <= 0 || nidx < 0 || (nidx > 0 && !idx)) return hipErrorInvalidValue;
+  if (B > (1ll << 40) || S > (1ll << 40) || (double)B * C * S >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
+  if (nidx == 0) return hipSuccess;
   long long total = B * nidx * S;
-  if (total == 0) return hipSuccess;
   unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 4096);
   tp::channel_fill<<<grid, 256, 0, st>>>(x, B, C, S, idx, nidx, value);
   return hipGetLastError();
@@ -81,7 +83,8 @@ extern "C" hipError_t tp_channel_fill(float* x, long long B, int C, long long S,
 
 extern "C" hipError_t tp_nan_channels(const float* x, long long B, int C, long long S, uint8_t* flags,
                                       hipStream_t st) {
-  if (C == 0) return hipSuccess;
+  if (!x || !flags || B <= 0 || C <= 0 || S <= 0) return hipErrorInvalidValue;
+  if (B > (1ll << 40) || S > (1ll << 40) || (double)B * C * S >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
   tp::nan_channels<<<C, 256, 0, st>>>(x, B, C, S, flags);
   return hipGetLastError();
 }
@@ -90,7 +93,15 @@ extern "C" hipError_t tp_nan_channels(const float* x, long long B, int C, long l
 extern "C" hipError_t tp_gather_multi(const void* const* srcs, void* const* dsts, const long long* outer,
                                       const long long* n, const long long* inner, int count, int elsize,
                                       const int64_t* keep, long long nkeep, hipStream_t st) {
-  if (count <= 0 || count > 8) return hipErrorInvalidValue;
+  if (count <= 0 || count > 8 || !srcs || !dsts || !outer || !n || !inner || nkeep < 0 || (nkeep > 0 && !keep))
+    return hipErrorInvalidValue;
+  if (elsize != 1 && elsize != 2 && elsize != 4 && elsize != 8) return hipErrorInvalidValue;
+  for (int i = 0; i < count; ++i) {
+    if (!srcs[i] || !dsts[i] || outer[i] < 0 || n[i] < 0 || inner[i] < 0) return hipErrorInvalidValue;
+    if (((uintptr_t)srcs[i] | (uintptr_t)dsts[i]) % (uintptr_t)elsize) return hipErrorInvalidValue;
+    if ((double)outer[i] * (double)std::max(n[i], nkeep) * (double)inner[i] >= 9.0e18) return hipErrorInvalidValue;
+  }
+  if (nkeep == 0) return hipSuccess;
   tp::GatherBatch b{};
   b.count = count;
   long long maxtot = 0;
@@ -186,6 +197,8 @@ __global__ __launch_bounds__(256) void unpool2_nhwc_v4(const float4* __restrict_
 
 extern "C" hipError_t tp_maxpool2_nhwc(const float* x, float* y, uint8_t* am, int B, int H, int W, int C,
                                        hipStream_t st) {
+  if (!x || !y || !am || B <= 0 || H < 2 || W < 2 || C <= 0 || (double)B * H * W * C >= 9.0e18)
+    return hipErrorInvalidValue;
   const long long total = (long long)B * (H / 2) * (W / 2) * C;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
   tp::maxpool2_nhwc<<<grid, 256, 0, st>>>(x, y, am, B, H, W, C);
@@ -194,6 +207,8 @@ extern "C" hipError_t tp_maxpool2_nhwc(const float* x, float* y, uint8_t* am, in
 
 extern "C" hipError_t tp_unpool2_nhwc(const float* g, const uint8_t* am, float* out, int B, int H, int W, int C,
                                       hipStream_t st) {
+  if (!g || !am || !out || B <= 0 || H < 2 || W < 2 || C <= 0 || (double)B * H * W * C >= 9.0e18)
+    return hipErrorInvalidValue;
   if (C % 4 == 0 && H % 2 == 0 && W % 2 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(am) & 3) == 0) {
     const long long total = (long long)B * (H / 2) * (W / 2) * (C / 4);
@@ -255,7 +270,10 @@ __global__ __launch_bounds__(256) void avgpool_nhwc(const float* __restrict__ x,
 
 extern "C" hipError_t tp_maxpool_nhwc(const float* x, float* y, int B, int H, int W, int C, int k, int s, int pad,
                                       hipStream_t st) {
-  if (C % 4 != 0) return hipErrorInvalidValue;
+  if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0) return hipErrorInvalidValue;
+  if (k < 1 || s < 1 || pad < 0 || 2ll * pad > k || k > H + 2ll * pad || k > W + 2ll * pad) return hipErrorInvalidValue;
+  if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) return hipErrorInvalidValue;  // float4 rows
+  if ((double)B * H * W * C >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
   const int Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
   const long long total = (long long)B * Ho * Wo * (C / 4);
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
@@ -264,6 +282,7 @@ extern "C" hipError_t tp_maxpool_nhwc(const float* x, float* y, int B, int H, in
 }
 
 extern "C" hipError_t tp_avgpool_nhwc(const float* x, float* y, int B, int HW, int C, hipStream_t st) {
+  if (!x || !y || B <= 0 || HW <= 0 || C <= 0 || (double)B * HW * C >= 9.0e18) return hipErrorInvalidValue;
   const long long total = (long long)B * C;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
   tp::avgpool_nhwc<<<grid, 256, 0, st>>>(x, y, B, HW, C);

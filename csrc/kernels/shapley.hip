@@ -101,7 +101,9 @@ __global__ __launch_bounds__(64) void shapley_column(const float* __restrict__ L
   if (threadIdx.x == 0) sv_col[perm[k0 + k]] += acc * scale;
 }
 
-// Fused softmax cross-entropy: per-sample loss and (optionally) dL/dlogits * gscale.
+// Fused softmax cross-entropy: per-sample loss and (optionally) dL/dlogits * gscale. A target outside
+// [0, NC) reads nothing: the row's loss and gradient are NaN (no ``ignore_index``: a criterion that
+// relies on it has to stay on the library path).
 __global__ __launch_bounds__(256) void cross_entropy_fb(const float* __restrict__ logits,
                                                         const int64_t* __restrict__ target,
                                                         float* __restrict__ loss, float* __restrict__ grad,
@@ -119,13 +121,14 @@ __global__ __launch_bounds__(256) void cross_entropy_fb(const float* __restrict_
   s = wave_sum(s);
   const float lse = m + __logf(s);
   const int64_t t = target[wave];
-  if (lane == 0) loss[wave] = lse - x[t];
+  const bool in_range = t >= 0 && t < NC;
+  if (lane == 0) loss[wave] = in_range ? lse - x[t] : __builtin_nanf("");
   if (grad) {
     float* g = grad + (long long)wave * NC;
     const float inv = 1.f / s;
     for (int j = lane; j < NC; j += 64) {
       float p = __expf(x[j] - m) * inv;
-      g[j] = (p - (j == t ? 1.f : 0.f)) * gscale;
+      g[j] = in_range ? (p - (j == t ? 1.f : 0.f)) * gscale : __builtin_nanf("");
     }
   }
 }
@@ -134,6 +137,10 @@ __global__ __launch_bounds__(256) void cross_entropy_fb(const float* __restrict_
 
 extern "C" hipError_t tp_prefix_mask(const float* z, float* out, const int* rank, long long N, int C, int S,
                                      int channels_last, int p0, int K, hipStream_t st) {
+  if (!z || !out || !rank || N <= 0 || C <= 0 || S <= 0 || p0 < 0 || K < 0) return hipErrorInvalidValue;
+  if (N % ((long long)C * S) != 0 || (long long)p0 + K >= (1ll << 31) || (((uintptr_t)z | (uintptr_t)out) & 3))
+    return hipErrorInvalidValue;
+  if ((double)N * K >= 9.0e18) return hipErrorInvalidValue;
   const bool vec = (N % 4 == 0) && (channels_last ? (C % 4 == 0) : (S % 4 == 0)) &&
                    (((uintptr_t)z | (uintptr_t)out) % 16 == 0);
   const long long total = (vec ? N / 4 : N) * K;
@@ -153,13 +160,20 @@ extern "C" hipError_t tp_prefix_mask(const float* z, float* out, const int* rank
 
 extern "C" hipError_t tp_shapley_scatter(const float* L, const int* perm, double* sv, int row0, int B, int n,
                                          int k0, int K, double scale, hipStream_t st) {
-  if (K * B == 0) return hipSuccess;
+  if (!L || !perm || !sv || B <= 0 || n <= 0 || row0 < 0 || k0 < 0 || K < 0 || (long long)k0 + K > n)
+    return hipErrorInvalidValue;
+  // the kernel's K * B and (k + 1) * B are 32-bit
+  if ((long long)(K + 1ll) * B >= (1ll << 31) || (long long)row0 + B >= (1ll << 31)) return hipErrorInvalidValue;
+  if (K == 0) return hipSuccess;
   tp::shapley_scatter<<<tp::ceil_div((long long)K * B, 256), 256, 0, st>>>(L, perm, sv, row0, B, n, k0, K, scale);
   return hipGetLastError();
 }
 
 extern "C" hipError_t tp_shapley_column(const float* L, const int* perm, double* sv_col, int B, int k0, int K,
                                         double scale, hipStream_t st) {
+  if (!L || !perm || !sv_col || B <= 0 || k0 < 0 || K < 0 || (long long)k0 + K >= (1ll << 31))
+    return hipErrorInvalidValue;
+  if ((long long)(K + 1ll) * B >= (1ll << 31)) return hipErrorInvalidValue;  // the kernel's (k + 1) * B is 32-bit
   if (K == 0) return hipSuccess;
   tp::shapley_column<<<K, 64, 0, st>>>(L, perm, sv_col, B, k0, scale);
   return hipGetLastError();
@@ -167,7 +181,8 @@ extern "C" hipError_t tp_shapley_column(const float* L, const int* perm, double*
 
 extern "C" hipError_t tp_cross_entropy(const float* logits, const int64_t* target, float* loss, float* grad,
                                        int B, int NC, float gscale, hipStream_t st) {
-  if (B == 0) return hipSuccess;
+  if (!logits || !target || !loss || B <= 0 || NC <= 0) return hipErrorInvalidValue;
+  if (B >= (1 << 25)) return hipErrorInvalidValue;  // one wave per row: the kernel's 32-bit thread index
   tp::cross_entropy_fb<<<tp::ceil_div((long long)B * 64, 256), 256, 0, st>>>(logits, target, loss, grad, B, NC,
                                                                             gscale);
   return hipGetLastError();
@@ -175,7 +190,8 @@ extern "C" hipError_t tp_cross_entropy(const float* logits, const int64_t* targe
 
 extern "C" hipError_t tp_prefix_tri_operands(const float* z, const float* W, const int* perm, int B, int C, int N,
                                              int p0, int cnt, int Kc, float* T, float* Wsub, hipStream_t st) {
-  if (cnt <= 0 || cnt > Kc || B <= 0 || N <= 0) return hipErrorInvalidValue;
+  if (!z || !W || !perm || !T || !Wsub || C <= 0 || p0 < 0) return hipErrorInvalidValue;
+  if (cnt <= 0 || cnt > Kc || B <= 0 || N <= 0 || (long long)p0 + cnt - 1 > C) return hipErrorInvalidValue;
   const long long total = (long long)cnt * B * Kc + (long long)N * Kc;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 8192);
   tp::prefix_tri_operands<<<grid, 256, 0, st>>>(z, W, perm, B, C, N, p0, cnt, Kc, T, Wsub);

@@ -9,12 +9,12 @@ namespace tp {
 
 struct Philox {
   static constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-  __device__ static uint4 round(uint4 c, uint2 k) {
+  __host__ __device__ static uint4 round(uint4 c, uint2 k) {
     const unsigned long long p0 = (unsigned long long)M0 * c.x, p1 = (unsigned long long)M1 * c.z;
     return make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k.x, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k.y, (unsigned)p0);
   }
   // 10 rounds on counter (ctr_lo, ctr_hi, 0, 0) with a 64-bit key
-  __device__ static uint4 gen(unsigned long long ctr, unsigned long long key) {
+  __host__ __device__ static uint4 gen(unsigned long long ctr, unsigned long long key) {
     uint4 c = make_uint4((unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u);
     uint2 k = make_uint2((unsigned)key, (unsigned)(key >> 32));
 #pragma unroll
@@ -54,12 +54,22 @@ __global__ void dropout_tail(const float* __restrict__ x, float* __restrict__ y,
 
 }  // namespace tp
 
+// The generator on the host (tests: the published Philox4x32-10 vectors, counters past 2^32).
+extern "C" void tp_philox4x32(unsigned long long ctr, unsigned long long key, unsigned* out) {
+  const uint4 r = tp::Philox::gen(ctr, key);
+  out[0] = r.x;
+  out[1] = r.y;
+  out[2] = r.z;
+  out[3] = r.w;
+}
+
 // y = dropout(x) (forward) or dx = dropout'(g) (backward: same seed, same call): the keep
 // decision is uint32 >= threshold with threshold = round(p * 2^32).
 extern "C" hipError_t tp_dropout(const float* x, float* y, long long n, unsigned long long seed, double p,
                                  hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  if (!(p >= 0.0 && p < 1.0) || ((uintptr_t)x | (uintptr_t)y) % 16) return hipErrorInvalidValue;
+  if (n < 0 || !(p >= 0.0 && p < 1.0)) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (!x || !y || ((uintptr_t)x | (uintptr_t)y) % 16) return hipErrorInvalidValue;
   const double th = p * 4294967296.0;
   const unsigned threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)th;
   const float scale = (float)(1.0 / (1.0 - p));
@@ -168,11 +178,13 @@ __global__ __launch_bounds__(256) void avgpool_bwd(const float* __restrict__ g, 
 
 extern "C" hipError_t tp_maxpool_fwd_arg(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, int k,
                                          int s, int pad, hipStream_t st) {
-  if (C % 4 || k < 1 || k * k > 255 || s < 1 || pad < 0 || 2 * pad > k) return hipErrorInvalidValue;
+  if (!x || !y || !am || B <= 0 || H <= 0 || W <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (C % 4 || k < 1 || k > 15 || s < 1 || pad < 0 || 2 * pad > k || k > H + 2ll * pad || k > W + 2ll * pad)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)x | (uintptr_t)y) & 15) || ((uintptr_t)am & 3)) return hipErrorInvalidValue;  // float4 / packed bytes
+  if ((double)B * H * W * C >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
   const int Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
-  if (Ho <= 0 || Wo <= 0) return hipErrorInvalidValue;
   const long long total = (long long)B * Ho * Wo * (C / 4);
-  if (total == 0) return hipSuccess;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
   tp::maxpool_fwd_arg<<<grid, 256, 0, st>>>(x, y, am, B, H, W, C, k, s, pad, Ho, Wo);
   return hipGetLastError();
@@ -180,10 +192,12 @@ extern "C" hipError_t tp_maxpool_fwd_arg(const float* x, float* y, uint8_t* am, 
 
 extern "C" hipError_t tp_maxpool_bwd(const float* g, const uint8_t* am, float* dx, int B, int H, int W, int C, int k,
                                      int s, int pad, hipStream_t st) {
-  if (C % 4 || k < 1 || k * k > 255 || s < 1 || pad < 0 || 2 * pad > k) return hipErrorInvalidValue;
+  if (!g || !am || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0) return hipErrorInvalidValue;
+  if (C % 4 || k < 1 || k > 15 || s < 1 || pad < 0 || 2 * pad > k || k > H + 2ll * pad || k > W + 2ll * pad)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)g | (uintptr_t)dx) & 15) || ((uintptr_t)am & 3)) return hipErrorInvalidValue;  // float4 / packed bytes
+  if ((double)B * H * W * C >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
   const int Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
-  const long long total = (long long)B * H * W * (C / 4);
-  if (total == 0) return hipSuccess;
   const int cpr = (int)tp::ceil_div((long long)W * (C / 4), 256);  // blocks per input row
   const long long blocks = (long long)B * H * cpr;
   if ((long long)W * (C / 4) >= (1ll << 31) || blocks >= (1ll << 31)) return hipErrorInvalidValue;
@@ -192,9 +206,10 @@ extern "C" hipError_t tp_maxpool_bwd(const float* g, const uint8_t* am, float* d
 }
 
 extern "C" hipError_t tp_avgpool_bwd(const float* g, float* dx, int B, int HW, int C, hipStream_t st) {
-  if (C % 4 || HW <= 0) return hipErrorInvalidValue;
+  if (!g || !dx || B <= 0 || C <= 0 || C % 4 || HW <= 0) return hipErrorInvalidValue;
+  if (((uintptr_t)g | (uintptr_t)dx) & 15) return hipErrorInvalidValue;  // float4 rows
+  if ((double)B * HW * C >= 9.0e18) return hipErrorInvalidValue;  // 64-bit offsets
   const long long total = (long long)B * HW * (C / 4);
-  if (total == 0) return hipSuccess;
   const unsigned grid = (unsigned)std::min<long long>(tp::ceil_div(total, 256), 16384);
   tp::avgpool_bwd<<<grid, 256, 0, st>>>(g, dx, B, HW, C);
   return hipGetLastError();

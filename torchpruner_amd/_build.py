@@ -382,3 +382,33 @@ def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
 if __name__ == "__main__":
     build(verbose=True, force="--force" in sys.argv)
     print(OUT)
+
+
+ELEMENTWISE_SOURCES = ("channel_reduce", "prune_ops", "shapley", "train_ops", "data_ops")
+
+
+def build_elementwise_sanitizer(verbose: bool = False) -> Path:
+    """Build ``csrc/tests/elementwise_validation.cpp`` against the launchers of the elementwise ops
+    (``channel_reduce.hip``, ``prune_ops.hip``, ``shapley.hip``, ``train_ops.hip``, ``data_ops.hip``)
+    with AddressSanitizer + UBSan on the HOST code only, like :func:`build_se_sanitizer`. Returns
+    the executable path."""
+    out_dir = ROOT / "build" / "asan"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    headers = sorted((CSRC / "include").glob("*.h"))
+    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    jobs, objs = [], []
+    for name in ELEMENTWISE_SOURCES:
+        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
+        objs.append(obj)
+        if _needs_rebuild(src, obj, headers):
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
+                         "-c", src, "-o", obj])
+    test_src, test_obj = CSRC / "tests" / "elementwise_validation.cpp", out_dir / "elementwise_validation.o"
+    if _needs_rebuild(test_src, test_obj, headers):
+        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
+    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 4)) as ex:
+        list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / "elementwise_validation"
+    if jobs or not exe.exists():
+        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
+    return exe

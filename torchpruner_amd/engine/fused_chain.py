@@ -1370,7 +1370,11 @@ def engine_criterion(criterion, device):
 
 
 def criterion_is_cross_entropy(criterion, device) -> bool:
-    """Numerically probe whether ``criterion(out, y[, reduction])`` is plain mean cross-entropy."""
+    """Numerically probe whether ``criterion(out, y[, reduction])`` is plain mean cross-entropy.
+
+    The probe uses in-range labels only, so ``F.cross_entropy`` itself passes it and runs on the fused
+    kernel, which does not implement ``ignore_index``: a label outside ``[0, classes)`` (``-100``
+    included) gives a NaN loss and a NaN gradient row there (``ops.cross_entropy``)."""
     try:
         g = torch.Generator(device="cpu").manual_seed(1234)
         logits = (torch.randn(6, 5, generator=g) * 2).to(device)

@@ -102,7 +102,11 @@ def score_fold_(Ts: Sequence[torch.Tensor], accs: Sequence[torch.Tensor | None],
         require().score_fold_(list(Ts), [a if a is not None else empty for a in accs], bool(take_abs), int(after))
         return
     for T, a in zip(Ts, accs):
-        tot = T.sum(0) if T.dim() == 3 else T
+        tot = T
+        if T.dim() == 3:  # in slot order, like the kernel
+            tot = T[0].clone()
+            for r in range(1, T.shape[0]):
+                tot += T[r]
         v = tot.abs() if take_abs else tot
         if a is not None:
             a += v.double().sum(0)
@@ -129,10 +133,8 @@ def nan_channels(x: torch.Tensor) -> torch.Tensor:
     """Bool (C,) mask: channel c carries a NaN anywhere in the batch/trailing dims."""
     if use_native(x) and x.dtype == torch.float32:
         return require().nan_channels(x).bool()
-    v = x
-    while v.dim() > 2:
-        v = v.sum(-1)
-    return torch.isnan(v.sum(0).flatten(0))
+    # (not isnan(x.sum(...)): +inf and -inf in one channel would sum to NaN)
+    return torch.isnan(x).transpose(0, 1).flatten(1).any(1)
 
 
 def gather_multi(tensors: Sequence[torch.Tensor], axes: Sequence[int], keep: torch.Tensor) -> list[torch.Tensor]:
@@ -210,15 +212,22 @@ def shapley_column(L: torch.Tensor, perm: torch.Tensor, sv_col: torch.Tensor, k0
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor, gscale: float = 1.0, want_grad: bool = True):
-    """Per-sample softmax cross-entropy and dL/dlogits * gscale (grad None if not wanted)."""
+    """Per-sample softmax cross-entropy and dL/dlogits * gscale (grad None if not wanted).
+
+    There is no ``ignore_index``: a target outside ``[0, classes)`` (``-100`` included) reads nothing
+    and gives a NaN loss and an all-NaN gradient row, on both paths."""
     if use_native(logits) and logits.dim() == 2:
         loss, grad = require().cross_entropy(logits.float(), target, float(gscale), bool(want_grad))
         return loss, (grad if want_grad else None)
     lf = logits.float()
-    loss = torch.nn.functional.cross_entropy(lf, target.long(), reduction="none")
+    t = target.long()
+    bad = (t < 0) | (t >= lf.shape[1])
+    t = t.masked_fill(bad, 0)
+    nan = torch.full((), float("nan"), dtype=lf.dtype, device=lf.device)
+    loss = torch.where(bad, nan, torch.nn.functional.cross_entropy(lf, t, reduction="none"))
     grad = None
     if want_grad:
         p = torch.softmax(lf, 1)
-        p[torch.arange(lf.shape[0]), target.long()] -= 1.0
-        grad = p * gscale
+        p[torch.arange(lf.shape[0]), t] -= 1.0
+        grad = torch.where(bad.unsqueeze(1), nan, p * gscale)
     return loss, grad
