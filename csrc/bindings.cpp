@@ -434,8 +434,8 @@ at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
   }
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty({B, (H + 2 * pad - k) / s + 1, (W + 2 * pad - k) / s + 1, C}, x.options());
-  TP_CHECK_HIP(tp_dwconv_fwd_cw(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)B, (int)H,
-                                (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
+  TP_CHECK_HIP(tp_dwconv_fwd(x.data_ptr<float>(), w.data_ptr<float>(), bp, y.data_ptr<float>(), (int)B, (int)H,
+                             (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
   return y;
 }
 
@@ -452,8 +452,8 @@ at::Tensor dwconv_dgrad(const at::Tensor& g_, const at::Tensor& w, int64_t H, in
               "dx exceeds the kernels' 2 GiB operand range");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   auto dx = at::empty({B, H, W, C}, g.options());
-  TP_CHECK_HIP(tp_dwconv_dgrad_cw(g.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H,
-                                  (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
+  TP_CHECK_HIP(tp_dwconv_dgrad(g.data_ptr<float>(), w.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H,
+                               (int)W, (int)C, (int)w.size(0), (int)k, (int)s, (int)pad, cur_stream()));
   return dx;
 }
 
@@ -485,10 +485,10 @@ c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x
   auto ws = at::empty({(int64_t)chunks * (k * k + 1) * C}, g.options().dtype(at::kDouble));
   c10::optional<at::Tensor> db;
   if (want_bias) db = at::empty({Cw}, g.options());
-  TP_CHECK_HIP(tp_dwconv_wgrad_cw(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
-                                  want_bias ? db->data_ptr<float>() : nullptr, ws.data_ptr<double>(), chunks, (int)B,
-                                  (int)H, (int)W, (int)C, (int)Cw, (int)k, (int)s, (int)pad, dw.stride(0),
-                                  dw.stride(2), dw.stride(3), cur_stream()));
+  TP_CHECK_HIP(tp_dwconv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
+                               want_bias ? db->data_ptr<float>() : nullptr, ws.data_ptr<double>(), chunks, (int)B,
+                               (int)H, (int)W, (int)C, (int)Cw, (int)k, (int)s, (int)pad, dw.stride(0),
+                               dw.stride(2), dw.stride(3), cur_stream()));
   return db;
 }
 

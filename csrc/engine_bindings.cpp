@@ -7,125 +7,6 @@
 
 #include "tp_launchers.h"
 
-extern "C" {
-hipError_t tp_conv_igemm(const float* x, const uint8_t* x_argmax, const float* w, int B, int H, int W, int Cin,
-                         int Cout, int ks, int pooled_m, int unpool, int epi, int cfg, int splits, const float* scale,
-                         const float* shift, int relu, float* out, uint8_t* out_argmax, const float* act,
-                         float* taylor, int HWo, int tay_group, float* ws, int tay_mode, float* apoz,
-                         float slope, hipStream_t st);
-int tp_conv_gen_k(int ks, int Cin);
-int tp_bn_groups(int P, int C);
-hipError_t tp_bn_fwd_train(const float* x, float* y, int P, int C, const float* gamma, const float* beta, float eps,
-                           float momentum, float* run_mean, float* run_var, float* mean, float* invstd, float* a,
-                           float* b, double* ws, hipStream_t st);
-hipError_t tp_bn_bwd_train(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                           const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a, float* k1,
-                           float* k2, double* ws, hipStream_t st);
-hipError_t tp_bn_fwd_train3(const float* x, float* y, int P, int C, const float* gamma, const float* beta, float eps,
-                            float momentum, float* run_mean, float* run_var, float* mean, float* invstd, float* a,
-                            float* b, double* ws, const float* res, int relu, uint8_t* mko, hipStream_t st);
-hipError_t tp_bn_bwd_train3(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                            const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a, float* k1,
-                            float* k2, double* ws, const float* ym, float* dres, const uint8_t* mk, hipStream_t st);
-hipError_t tp_bn_fwd_train2(const float* x, float* y, int P, int C, const float* gamma, const float* beta, float eps,
-                            float momentum, float* run_mean, float* run_var, float* mean, float* invstd, float* a,
-                            float* b, double* ws, const float* res, int relu, hipStream_t st);
-hipError_t tp_bn_bwd_train2(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                            const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a, float* k1,
-                            float* k2, double* ws, const float* ym, float* dres, hipStream_t st);
-hipError_t tp_conv_wgrad(const float* g, const float* x, float* dw, float* ws, int B, int H, int W, int Cin, int Cout,
-                         int ks, int stride, int pad, int Kpad, int cfg, int splits, hipStream_t st);
-hipError_t tp_conv_gen2(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks, int stride,
-                        int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits, const float* scale,
-                        const float* shift, int relu, const float* res, int res_stride, const float* mask,
-                        float* apoz, float* out, float* ws, hipStream_t st);
-hipError_t tp_conv_gen(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks, int stride,
-                       int pad, int cfg, int splits, const float* scale, const float* shift, int relu,
-                       const float* res, float* apoz, float* out, float* ws, hipStream_t st);
-hipError_t tp_maxpool_nhwc(const float* x, float* y, int B, int H, int W, int C, int k, int s, int pad,
-                           hipStream_t st);
-hipError_t tp_avgpool_nhwc(const float* x, float* y, int B, int HW, int C, hipStream_t st);
-hipError_t tp_maxpool2_nhwc(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, hipStream_t st);
-hipError_t tp_unpool2_nhwc(const float* g, const uint8_t* am, float* out, int B, int H, int W, int C, hipStream_t st);
-hipError_t tp_conv_first_wave(const float* x, const float* wt, const float* scale, const float* shift, float* out,
-                              int B, int Cin, int H, int W, int Cout, int relu, hipStream_t st);
-hipError_t tp_conv_first_direct(const float* x, const float* w, const float* scale, const float* shift, float* out,
-                                int B, int Cin, int H, int W, int Cout, int relu, hipStream_t st);
-int tp_wino_taylor_slots(int H, int W);
-int tp_wino_lds_bytes();
-int tp_wino_staged_ok(int H, int W, int unpool);
-hipError_t tp_nchw_to_nhwc_pad(const float* x, float* y, int B, int C, int H, int W, int Cp, hipStream_t st);
-hipError_t tp_conv_wino(const float* x, const uint8_t* x_argmax, const float* u, int B, int H, int W, int C, int K,
-                        int unpool, int epi, int splits, int staged, const float* scale, const float* shift, int relu,
-                        float* out, uint8_t* out_argmax, const float* act, float* taylor, float* apoz, float* ws,
-                        int tay_mode, hipStream_t st);
-hipError_t tp_wino_weights(const float* w, float* u, int K, int C, int flip_t, hipStream_t st);
-hipError_t tp_wino_weights2(const float* w, float* u, int K, int C, int flip_t, int S0, int S1, hipStream_t st);
-hipError_t tp_wino_weights_bf16(const float* w, void* u, int K, int C, int flip_t, int S0, int S1, hipStream_t st);
-hipError_t tp_pack_conv_weights_multi(const long long* desc, int n, long long total, hipStream_t st);
-hipError_t tp_pack_conv_weight(const float* w, float* out, int O, int I, int KS, int rows, int cols, int cpad, int mode,
-                               hipStream_t st);
-long long tp_wino_wgrad_ws_elems(int B, int H, int W, int Cin, int Cout, int splits);
-hipError_t tp_wino_wgrad(const float* g, const float* x, float* ws, int B, int H, int W, int Cin, int Cout, int cfg,
-                         int splits, float* fin, int fin_co, int fin_ci, const long long* fs, hipStream_t st);
-hipError_t tp_conv_gen3(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks, int stride,
-                        int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits, const float* scale,
-                        const float* shift, int relu, const float* res, int res_stride, const float* mask,
-                        float* apoz, float* out, float* ws, double* bnpart, hipStream_t st);
-int tp_conv_tile_m(int cfg);
-long long tp_conv_sk_ws_floats(int cfg, int ks, int transposed, int tay, int M, int N);
-hipError_t tp_conv_gen4(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks, int stride,
-                        int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits, const float* scale,
-                        const float* shift, int relu, const float* res, int res_stride, const float* mask,
-                        float* apoz, float* out, float* ws, double* bnpart, float* tay_part, int tay_mode,
-                        hipStream_t st);
-int tp_conv_gen_tay_slots(int cfg, int HWo);
-hipError_t tp_conv_gen5(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks, int stride,
-                        int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits, const float* scale,
-                        const float* shift, int relu, const float* res, int res_stride, const float* mask,
-                        float* apoz, float* out, float* ws, double* bnpart, float* tay_part, int tay_mode,
-                        const uint8_t* res_bits, const float* bnb_y, const float* bnb_mean, const float* bnb_invstd,
-                        const uint8_t* bnb_bits, hipStream_t st);
-hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float* dx, int P, int C, int Cr, const float* gamma,
-                               const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a,
-                               float* k1, float* k2, double* ws, const double* pre, int G, const float* ym,
-                               float* dres, const uint8_t* mk, hipStream_t st);
-hipError_t tp_bn_fwd_train_pre2(const float* x, float* y, int P, int C, int Cr, const float* gamma,
-                                const float* beta, float eps, float momentum, float* run_mean, float* run_var,
-                                float* mean, float* invstd, float* a, float* b, double* ws, const double* pre, int G,
-                                const float* res, int relu, uint8_t* mko, long long* nbt, hipStream_t st);
-hipError_t tp_bn_fwd_train5(const float* x, float* y, int P, int C, int Cr, const float* gamma, const float* beta,
-                            float eps, float momentum, float* run_mean, float* run_var, float* mean, float* invstd,
-                            float* a, float* b, double* ws, const float* res, int relu, uint8_t* mko, long long* nbt,
-                            hipStream_t st);
-hipError_t tp_bn_bwd_train4(const float* g, const float* x, float* dx, int P, int C, int Cr, const float* gamma,
-                            const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a, float* k1,
-                            float* k2, double* ws, const float* ym, float* dres, const uint8_t* mk, hipStream_t st);
-hipError_t tp_conv_wgrad2(const float* g, const float* x, float* dw, float* ws, int B, int H, int W, int Cin, int Cout,
-                          int ks, int stride, int pad, int Kpad, int cfg, int splits, float* fin, int fin_co,
-                          int fin_ci, const long long* fs, hipStream_t st);
-hipError_t tp_prefix_delta_gemm(const float* T, const float* Wsub, const float* neg_one, const float* Y0, int M, int Kc,
-                                int N, int B0, int relu, float slope, int cfg, float* out, hipStream_t st);
-hipError_t tp_prefix_tri_operands(const float* z, const float* W, const int* perm, int B, int C, int N, int p0,
-                                  int cnt, int Kc, float* T, float* Wsub, hipStream_t st);
-hipError_t tp_wino4_weights(const float* w, float* u, int K, int C, int flip_t, int S0, int S1, hipStream_t st);
-hipError_t tp_wino4_weights_multi(const long long* desc, int n, long long total, hipStream_t st);
-hipError_t tp_wino4_weights_strided(const float* w, float* u, int K, int C, int flip_t, int S0, int S1, long long st0,
-                                    long long st1, int st2, int st3, hipStream_t st);
-int tp_wino4_u_img();
-int tp_wino4_ok(int H, int W, int C, int K);
-int tp_wino4_taylor_slots(int S);
-int tp_wino4_lds_bytes(int S, int variant);
-hipError_t tp_conv_wino4_ko(const float* x, const float* u, int B, int S, int C, int K, int epi, const float* scale,
-                           const float* shift, int relu, float* out, uint8_t* out_argmax, const float* act,
-                           float* taylor, float* apoz, int tay_mode, int splits, float* ws, int variant,
-                           hipStream_t st, const uint8_t* unpool_am, int ko);
-hipError_t tp_conv_wino4(const float* x, const float* u, int B, int S, int C, int K, int epi, const float* scale,
-                         const float* shift, int relu, float* out, uint8_t* out_argmax, const float* act, float* taylor,
-                         float* apoz, int tay_mode, int splits, float* ws, int variant, hipStream_t st,
-                         const uint8_t* unpool_am);
-}
-
 namespace {
 
 inline hipStream_t cur_stream() { return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
@@ -385,8 +266,8 @@ at::Tensor wino_weights(const at::Tensor& w, bool flip_t, int64_t K, int64_t C, 
     TP_CHECK_HIP(tp_wino_weights_bf16(w.data_ptr<float>(), u.data_ptr(), (int)K, (int)C, flip_t ? 1 : 0,
                                       (int)w.size(0), (int)w.size(1), cur_stream()));
   else
-    TP_CHECK_HIP(tp_wino_weights2(w.data_ptr<float>(), u.data_ptr<float>(), (int)K, (int)C, flip_t ? 1 : 0,
-                                  (int)w.size(0), (int)w.size(1), cur_stream()));
+    TP_CHECK_HIP(tp_wino_weights(w.data_ptr<float>(), u.data_ptr<float>(), (int)K, (int)C, flip_t ? 1 : 0,
+                                 (int)w.size(0), (int)w.size(1), cur_stream()));
   return u;
 }
 
@@ -703,10 +584,10 @@ std::tuple<at::Tensor, at::Tensor> conv_wino4_fwd(const at::Tensor& x, const at:
   const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, C / 8));
   at::Tensor ws;
   if (sp > 1) ws = at::empty({sp * B * H * W * K}, x.options());
-  TP_CHECK_HIP(tp_conv_wino4_ko(x.data_ptr<float>(), u.data_ptr<float>(), (int)B, (int)H, (int)C, (int)Kc,
-                                pool ? EPI_FWD_POOL : EPI_FWD, sc, sh, relu ? 1 : 0, out.data_ptr<float>(),
-                                pool ? am.data_ptr<uint8_t>() : nullptr, nullptr, nullptr, ap, 0, (int)sp,
-                                sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), nullptr, (int)K));
+  TP_CHECK_HIP(tp_conv_wino4(x.data_ptr<float>(), u.data_ptr<float>(), (int)B, (int)H, (int)C, (int)Kc,
+                             pool ? EPI_FWD_POOL : EPI_FWD, sc, sh, relu ? 1 : 0, out.data_ptr<float>(),
+                             pool ? am.data_ptr<uint8_t>() : nullptr, nullptr, nullptr, ap, 0, (int)sp,
+                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), nullptr, (int)K));
   return {out, am};
 }
 
@@ -753,10 +634,10 @@ at::Tensor conv_wino4_dgrad(const at::Tensor& g, const at::Tensor& ut, const at:
   if (want_out) out = unp ? at::empty({B, 2 * H, 2 * W, Cin}, g.options()) : at::empty({B, H, W, Cin}, g.options());
   at::Tensor ws;
   if (sp > 1) ws = at::empty({sp * B * H * W * Cin}, g.options());
-  TP_CHECK_HIP(tp_conv_wino4_ko(g.data_ptr<float>(), ut.data_ptr<float>(), (int)B, (int)H, (int)Cout, (int)Kc,
-                                EPI_BWD, sc, nullptr, 0, want_out ? out.data_ptr<float>() : nullptr, nullptr,
-                                act.data_ptr<float>(), tay, nullptr, (int)tay_mode, (int)sp,
-                                sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), unp, (int)Cin));
+  TP_CHECK_HIP(tp_conv_wino4(g.data_ptr<float>(), ut.data_ptr<float>(), (int)B, (int)H, (int)Cout, (int)Kc,
+                             EPI_BWD, sc, nullptr, 0, want_out ? out.data_ptr<float>() : nullptr, nullptr,
+                             act.data_ptr<float>(), tay, nullptr, (int)tay_mode, (int)sp,
+                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), unp, (int)Cin));
   return out;
 }
 
@@ -824,8 +705,9 @@ at::Tensor conv_gen(const at::Tensor& x, const at::Tensor& w, const c10::optiona
     cf = cfg & ~kCfgSK;
   }
   TP_CHECK_HIP(tp_conv_gen(x.data_ptr<float>(), w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                           (int)ks, (int)stride, (int)pad, (int)cf, (int)sp, sc, sh, relu ? 1 : 0, rp, ap,
-                           out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr, cur_stream()));
+                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)cf, (int)sp, sc, sh, relu ? 1 : 0, rp, 1,
+                           nullptr, ap, out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr,
+                           nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, cur_stream()));
   return out;
 }
 
@@ -961,11 +843,11 @@ at::Tensor conv_gen_bwd(const at::Tensor& g, const at::Tensor& wt, const c10::op
   } else if (cfg >= 0) {
     cf = cfg & ~kCfgSK;
   }
-  TP_CHECK_HIP(tp_conv_gen4(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N,
-                            (int)ks, (int)stride, (int)pad, transposed ? 1 : 0, (int)Ho, (int)Wo, (int)cf, (int)sp,
-                            nullptr, nullptr, 0, rp, (int)res_stride, mp, nullptr, out.data_ptr<float>(),
-                            ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, tp_, (int)tay_mode,
-                            cur_stream()));
+  TP_CHECK_HIP(tp_conv_gen(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N,
+                           (int)ks, (int)stride, (int)pad, transposed ? 1 : 0, (int)Ho, (int)Wo, (int)cf, (int)sp,
+                           nullptr, nullptr, 0, rp, (int)res_stride, mp, nullptr, out.data_ptr<float>(),
+                           ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, tp_, (int)tay_mode, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, cur_stream()));
   return out;
 }
 
@@ -981,7 +863,7 @@ static const uint8_t* bit_mask_ptr(const c10::optional<at::Tensor>& t, int64_t e
 }
 
 // Data gradient of a 1x1 stride-1 conv (the training path's residual-block conv1) with the two
-// fusions of a bottleneck's backward (tp_conv_gen5):
+// fusions of a bottleneck's backward (tp_conv_gen):
 //   res_bits: ``res`` is the raw gradient of the block output's ReLU, masked here by its bit mask;
 //   bn_y / bn_mean / bn_invstd (/ bn_bits): the output gradient reaches a BatchNorm (+ ReLU) whose
 //     backward statistics (sum gm, sum gm * xhat) come back per M tile, [tiles][2][N] fp64.
@@ -1027,10 +909,10 @@ std::tuple<at::Tensor, at::Tensor> conv_gen_bwd_bn(const at::Tensor& g, const at
   auto out = at::empty({B, H, W, N}, g.options());
   at::Tensor ws = sk_workspace(cfg, 1, false, false, M, N, g.options());
   const int64_t cf = ws.defined() || cfg < 0 ? cfg : cfg & ~kCfgSK;
-  TP_CHECK_HIP(tp_conv_gen5(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N, 1, 1,
-                            0, 0, 0, 0, (int)cf, 1, nullptr, nullptr, 0, rp, (int)res_stride, nullptr, nullptr,
-                            out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
-                            yp ? part.data_ptr<double>() : nullptr, nullptr, 0, rb, yp, mp, ip, bb, cur_stream()));
+  TP_CHECK_HIP(tp_conv_gen(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N, 1, 1,
+                           0, 0, 0, 0, (int)cf, 1, nullptr, nullptr, 0, rp, (int)res_stride, nullptr, nullptr,
+                           out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
+                           yp ? part.data_ptr<double>() : nullptr, nullptr, 0, rb, yp, mp, ip, bb, cur_stream()));
   return {out, part};
 }
 
@@ -1077,10 +959,10 @@ at::Tensor conv_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t ks, int6
   sp = (slices + per - 1) / per;
   at::Tensor ws;
   if (sp > 1) ws = at::empty({sp * Cout * Kpad}, g.options());
-  TP_CHECK_HIP(tp_conv_wgrad2(g.data_ptr<float>(), x.data_ptr<float>(), fin ? nullptr : dw.data_ptr<float>(),
-                              sp > 1 ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                              (int)ks, (int)stride, (int)pad, (int)Kpad, (int)cfg, (int)sp, fin, fco, fci,
-                              fin ? fs : nullptr, cur_stream()));
+  TP_CHECK_HIP(tp_conv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), fin ? nullptr : dw.data_ptr<float>(),
+                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
+                             (int)ks, (int)stride, (int)pad, (int)Kpad, (int)cfg, (int)sp, fin, fco, fci,
+                             fin ? fs : nullptr, 1, 0, 0, cur_stream()));
   return fin ? at::empty({0}, g.options()) : dw;  // with ``out`` the result is in ``out``
 }
 
@@ -1106,10 +988,11 @@ std::tuple<at::Tensor, at::Tensor> conv_gen_stats(const at::Tensor& x, const at:
   auto part = at::empty({(M + tm - 1) / tm, 2, Cout}, x.options().dtype(at::kDouble));
   at::Tensor ws = Cin != 4 ? sk_workspace(cfg, ks, false, false, M, Cout, x.options()) : at::Tensor();
   const int64_t cf = ws.defined() || cfg < 0 ? cfg : cfg & ~kCfgSK;
-  TP_CHECK_HIP(tp_conv_gen3(x.data_ptr<float>(), w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                            (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)cf, 1, nullptr, sh, 0, nullptr, 1, nullptr,
-                            nullptr, out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
-                            part.data_ptr<double>(), cur_stream()));
+  TP_CHECK_HIP(tp_conv_gen(x.data_ptr<float>(), w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
+                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)cf, 1, nullptr, sh, 0, nullptr, 1, nullptr,
+                           nullptr, out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
+                           part.data_ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           cur_stream()));
   return {out, part};
 }
 
@@ -1199,16 +1082,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
                 "pre must be conv_gen_stats' (G, 2, C) fp64 tile statistics");
     const int64_t G = pre->size(0);
     auto ws = at::empty({2 * std::min<int64_t>(G, 256) * C}, x.options().dtype(at::kDouble));
-    TP_CHECK_HIP(tp_bn_fwd_train_pre2(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
-                                     (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(),
-                                     pre->data_ptr<double>(), (int)G, rp, act,
-                                     act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
+    TP_CHECK_HIP(tp_bn_fwd_train_pre(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
+                                    (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(),
+                                    pre->data_ptr<double>(), (int)G, rp, act,
+                                    act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
     return {y, stats[0], stats[1], mk};
   }
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
-  TP_CHECK_HIP(tp_bn_fwd_train5(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
-                                (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(), rp,
-                                act, act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
+  TP_CHECK_HIP(tp_bn_fwd_train(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
+                               (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(), rp,
+                               act, act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
   return {y, stats[0], stats[1], mk};
 }
 
@@ -1268,10 +1151,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
     return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
   }
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
-  TP_CHECK_HIP(tp_bn_bwd_train4(g.data_ptr<float>(), x.data_ptr<float>(), want_dx ? dx.data_ptr<float>() : nullptr,
-                                (int)P, (int)C, (int)Cr, ga, mp, ip, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
-                                ws.data_ptr<double>(), mkp ? nullptr : yp, want_dres ? dres.data_ptr<float>() : nullptr,
-                                mkp, cur_stream()));
+  TP_CHECK_HIP(tp_bn_bwd_train(g.data_ptr<float>(), x.data_ptr<float>(), want_dx ? dx.data_ptr<float>() : nullptr,
+                               (int)P, (int)C, (int)Cr, ga, mp, ip, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
+                               ws.data_ptr<double>(), mkp ? nullptr : yp, want_dres ? dres.data_ptr<float>() : nullptr,
+                               mkp, cur_stream()));
   return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
 }
 

@@ -16,6 +16,7 @@
 // A block owns a 64-wide column quad range (16 threads x float4) x 16 row lanes, and walks
 // rows_per_group rows; the 16 row lanes are folded in LDS in a fixed order.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 
@@ -437,10 +438,10 @@ static void partial_launch(dim3 grid, const float* x, const float* g, const floa
 // 1 ReLU, 2 ReLU6 (needs mko); anything else is rejected.
 // mko (nullable for ReLU, with an activation only): the bit mask, ceil(P*C/4) bytes (byte i, bit q =
 // the gradient passes at flat element 4i+q: > 0 for ReLU, strictly inside (0, 6) for ReLU6)
-extern "C" hipError_t tp_bn_fwd_train5(const float* x, float* y, int P, int C, int Cr, const float* gamma,
-                                       const float* beta, float eps, float momentum, float* run_mean, float* run_var,
-                                       float* mean, float* invstd, float* a, float* b, double* ws, const float* res,
-                                       int relu, uint8_t* mko, long long* nbt, hipStream_t st) {
+extern "C" hipError_t tp_bn_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                      const float* beta, float eps, float momentum, float* run_mean, float* run_var,
+                                      float* mean, float* invstd, float* a, float* b, double* ws, const float* res,
+                                      int relu, uint8_t* mko, long long* nbt, hipStream_t st) {
   using namespace tp;
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
   if (!bn_act_ok(relu, mko)) return hipErrorInvalidValue;
@@ -454,22 +455,14 @@ extern "C" hipError_t tp_bn_fwd_train5(const float* x, float* y, int P, int C, i
   return hipGetLastError();
 }
 
-extern "C" hipError_t tp_bn_fwd_train4(const float* x, float* y, int P, int C, const float* gamma, const float* beta,
-                                       float eps, float momentum, float* run_mean, float* run_var, float* mean,
-                                       float* invstd, float* a, float* b, double* ws, const float* res, int relu,
-                                       uint8_t* mko, long long* nbt, hipStream_t st) {
-  return tp_bn_fwd_train5(x, y, P, C, C, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd, a, b, ws, res,
-                          relu, mko, nbt, st);
-}
-
 // Forward with the batch statistics already reduced per conv tile (``pre``: [G][2][C] sums and
 // sums of squares over the tiles' rows, from the producing conv's epilogue): no statistics pass
 // over x. ws holds 2 * min(G, 256) * C doubles.
-extern "C" hipError_t tp_bn_fwd_train_pre2(const float* x, float* y, int P, int C, int Cr, const float* gamma,
-                                           const float* beta, float eps, float momentum, float* run_mean,
-                                           float* run_var, float* mean, float* invstd, float* a, float* b,
-                                           double* ws, const double* pre, int G, const float* res, int relu,
-                                           uint8_t* mko, long long* nbt, hipStream_t st) {
+extern "C" hipError_t tp_bn_fwd_train_pre(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                          const float* beta, float eps, float momentum, float* run_mean,
+                                          float* run_var, float* mean, float* invstd, float* a, float* b,
+                                          double* ws, const double* pre, int G, const float* res, int relu,
+                                          uint8_t* mko, long long* nbt, hipStream_t st) {
   using namespace tp;
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || G <= 0 || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
   if (!bn_act_ok(relu, mko)) return hipErrorInvalidValue;
@@ -482,47 +475,14 @@ extern "C" hipError_t tp_bn_fwd_train_pre2(const float* x, float* y, int P, int 
   return hipGetLastError();
 }
 
-extern "C" hipError_t tp_bn_fwd_train_pre(const float* x, float* y, int P, int C, const float* gamma,
-                                          const float* beta, float eps, float momentum, float* run_mean,
-                                          float* run_var, float* mean, float* invstd, float* a, float* b,
-                                          double* ws, const double* pre, int G, const float* res, int relu,
-                                          uint8_t* mko, long long* nbt, hipStream_t st) {
-  return tp_bn_fwd_train_pre2(x, y, P, C, C, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd, a, b, ws,
-                              pre, G, res, relu, mko, nbt, st);
-}
-
-// num_batches_tracked-free entry (``nbt`` = null)
-extern "C" hipError_t tp_bn_fwd_train3(const float* x, float* y, int P, int C, const float* gamma, const float* beta,
-                                       float eps, float momentum, float* run_mean, float* run_var, float* mean,
-                                       float* invstd, float* a, float* b, double* ws, const float* res, int relu,
-                                       uint8_t* mko, hipStream_t st) {
-  return tp_bn_fwd_train4(x, y, P, C, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd, a, b, ws, res, relu,
-                          mko, nullptr, st);
-}
-
-extern "C" hipError_t tp_bn_fwd_train2(const float* x, float* y, int P, int C, const float* gamma, const float* beta,
-                                       float eps, float momentum, float* run_mean, float* run_var, float* mean,
-                                       float* invstd, float* a, float* b, double* ws, const float* res, int relu,
-                                       hipStream_t st) {
-  return tp_bn_fwd_train3(x, y, P, C, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd, a, b, ws, res, relu,
-                          nullptr, st);
-}
-
-extern "C" hipError_t tp_bn_fwd_train(const float* x, float* y, int P, int C, const float* gamma, const float* beta,
-                                      float eps, float momentum, float* run_mean, float* run_var, float* mean,
-                                      float* invstd, float* a, float* b, double* ws, hipStream_t st) {
-  return tp_bn_fwd_train2(x, y, P, C, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd, a, b, ws, nullptr,
-                          0, st);
-}
-
 // Backward of the fused tail: ym = the block output y (ReLU mask; nullable), dres = gradient of
 // the residual input (nullable). dx nullable (dgamma / dbeta only). Channels c >= Cr: padding
 // (dx = 0 there, no dgamma / dbeta written).
 // mk (nullable): the forward's ReLU bit mask, used instead of ym
-extern "C" hipError_t tp_bn_bwd_train4(const float* g, const float* x, float* dx, int P, int C, int Cr,
-                                       const float* gamma, const float* mean, const float* invstd, float* dgamma,
-                                       float* dbeta, float* a, float* k1, float* k2, double* ws, const float* ym,
-                                       float* dres, const uint8_t* mk, hipStream_t st) {
+extern "C" hipError_t tp_bn_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
+                                      const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                                      float* dbeta, float* a, float* k1, float* k2, double* ws, const float* ym,
+                                      float* dres, const uint8_t* mk, hipStream_t st) {
   using namespace tp;
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
   const int groups = bn_groups(P, C);
@@ -537,7 +497,7 @@ extern "C" hipError_t tp_bn_bwd_train4(const float* g, const float* x, float* dx
 }
 
 // Backward with the statistics (sum gm, sum gm * xhat) already reduced per conv tile by the GEMM
-// epilogue that produced g (``pre``: [G][2][C], tp_conv_gen5's bnb mode): no statistics pass over
+// epilogue that produced g (``pre``: [G][2][C], tp_conv_gen's bnb mode): no statistics pass over
 // g and x. ws holds 2 * min(G, 256) * C doubles.
 extern "C" hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float* dx, int P, int C, int Cr,
                                           const float* gamma, const float* mean, const float* invstd, float* dgamma,
@@ -553,24 +513,4 @@ extern "C" hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float*
   if (dx || dres)
     apply_launch<true>(x, g, a, k1, k2, dx, P, C, nullptr, 0, ym, dres, const_cast<uint8_t*>(mk), st);
   return hipGetLastError();
-}
-
-extern "C" hipError_t tp_bn_bwd_train3(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                                       const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a,
-                                       float* k1, float* k2, double* ws, const float* ym, float* dres,
-                                       const uint8_t* mk, hipStream_t st) {
-  return tp_bn_bwd_train4(g, x, dx, P, C, C, gamma, mean, invstd, dgamma, dbeta, a, k1, k2, ws, ym, dres, mk, st);
-}
-
-extern "C" hipError_t tp_bn_bwd_train2(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                                       const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a,
-                                       float* k1, float* k2, double* ws, const float* ym, float* dres,
-                                       hipStream_t st) {
-  return tp_bn_bwd_train3(g, x, dx, P, C, gamma, mean, invstd, dgamma, dbeta, a, k1, k2, ws, ym, dres, nullptr, st);
-}
-
-extern "C" hipError_t tp_bn_bwd_train(const float* g, const float* x, float* dx, int P, int C, const float* gamma,
-                                      const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a,
-                                      float* k1, float* k2, double* ws, hipStream_t st) {
-  return tp_bn_bwd_train2(g, x, dx, P, C, gamma, mean, invstd, dgamma, dbeta, a, k1, k2, ws, nullptr, nullptr, st);
 }

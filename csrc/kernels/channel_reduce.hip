@@ -7,6 +7,7 @@
 // and a second deterministic column pass folds it into fp64 running sums. There is no
 // host sync per batch and no float atomics (bit-reproducible results).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

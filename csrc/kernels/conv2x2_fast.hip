@@ -15,10 +15,7 @@
 // algorithm on the flipped, transposed weight. The coefficients are 0 and +-1 only: the fp32
 // error stays at the 1e-6 level (V sums at most 4 pixels, Y at most 4 products).
 #include "tp_common.h"
-
-extern "C" int tp_conv_norm_splits(int splits, int K);
-extern "C" hipError_t tp_conv_igemm_batched(const float* x, const float* w, int nbatch, int M, int K, int N, int cfg,
-                                            int splits, float* slabs, hipStream_t st);
+#include "tp_launchers.h"
 
 namespace tp {
 

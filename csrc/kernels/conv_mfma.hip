@@ -18,6 +18,7 @@
 // accumulator layout (row = (r&3) + 8(r>>2) + 4(lane>>5)) places in ONE lane's registers
 // r = 4g..4g+3 — the max-pool is four in-register max operations.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 #include <cstdlib>
 
@@ -88,7 +89,7 @@ struct ConvArgs {
   float* tay_part;          // GEN EPI_FWD LDS epilogue with a mask (data gradient), no split: Taylor
                             // partials -(v * mask) (tay_mode 1: |v|) per (image, column) of every M
                             // tile, slot r = m_tile - first tile of the image: [R][B][N], one writer each
-  // stream-K (GEN 1, one K pass; see tp_conv_gen4): sk_blocks = P > 0 blocks share the tiles x
+  // stream-K (GEN 1, one K pass; see tp_conv_gen): sk_blocks = P > 0 blocks share the tiles x
   // k-slices iteration space in equal contiguous ranges; a tile cut by a range boundary f has its
   // two raw partial accumulator sets in sk_ws[f][0 / 1] (BM * BN floats each) and gets its
   // epilogue from the fixup launch (sk_fixup = 1, block f): slot 0 + slot 1 in that fixed order
@@ -96,7 +97,7 @@ struct ConvArgs {
   int sk_fixup;
   long long sk_iters;
   float* sk_ws;
-  // training data gradient of a residual block's conv1 (GEN 1, res_stride 1; see tp_conv_gen5):
+  // training data gradient of a residual block's conv1 (GEN 1, res_stride 1; see tp_conv_gen):
   const uint8_t* res_bits;  // the residual is the raw gradient of the block's ReLU output: masked here by
                             // that ReLU's bit mask (byte (pix*N + n) / 4, bit n % 4), so the BN
                             // backward never writes the masked copy
@@ -1670,19 +1671,6 @@ extern "C" int tp_conv_gen_k(int ks, int Cin) {
   return Cin == 4 ? (ks * ks * 4 + 31) / 32 * 32 : ks * ks * ((Cin + 31) / 32 * 32);
 }
 
-extern "C" hipError_t tp_conv_gen2(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   hipStream_t st);
-
-extern "C" hipError_t tp_conv_gen(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                  int stride, int pad, int cfg, int splits, const float* scale, const float* shift,
-                                  int relu, const float* res, float* apoz, float* out, float* ws, hipStream_t st) {
-  return tp_conv_gen2(x, w, B, H, W, Cin, Cout, ks, stride, pad, 0, 0, 0, cfg, splits, scale, shift, relu, res, 1,
-                      nullptr, apoz, out, ws, st);
-}
-
 // Shapley prefix-delta GEMM (see prefix_tri_operands in shapley.hip):
 //   out[r, n] = act(Y0[r % B0, n] - (T @ Wsub^T)[r, n]),  T (M, Kc), Wsub (N, Kc), Y0 (B0, N)
 // on the GEN 1x1 kernel: scale = -1 (a device vector), residual Y0 broadcast by res_rows = B0,
@@ -1718,24 +1706,6 @@ extern "C" hipError_t tp_prefix_delta_gemm(const float* T, const float* Wsub, co
   return gen_dispatch<EPI_FWD>(1, 1, cfg, a, 1, st);
 }
 
-// Full entry: ``transposed`` = data gradient of a strided conv (GEN 3) producing Ho_t x Wo_t
-// (the forward conv's input size); ``mask`` = ReLU-backward activation; ``res_stride``: see
-// ConvArgs. Forward convs pass transposed = 0 (Ho_t/Wo_t ignored), mask = null, res_stride = 1.
-extern "C" hipError_t tp_conv_gen3(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, hipStream_t st);
-
-extern "C" hipError_t tp_conv_gen2(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   hipStream_t st) {
-  return tp_conv_gen3(x, w, B, H, W, Cin, Cout, ks, stride, pad, transposed, Ho_t, Wo_t, cfg, splits, scale, shift,
-                      relu, res, res_stride, mask, apoz, out, ws, nullptr, st);
-}
-
 // M tile height of an implicit-GEMM tile config (the row count of a bnpart slab is ceil(M / it))
 extern "C" int tp_conv_tile_m(int cfg) {
   switch (cfg & ~(tp::CFG_SK | tp::CFG_SB)) {
@@ -1745,13 +1715,7 @@ extern "C" int tp_conv_tile_m(int cfg) {
   }
 }
 
-extern "C" hipError_t tp_conv_gen4(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, float* tay_part, int tay_mode, hipStream_t st);
-
-// Taylor partial slots of tp_conv_gen4's ``tay_part`` for tile config cfg at Ho*Wo output pixels
+// Taylor partial slots of tp_conv_gen's ``tay_part`` for tile config cfg at Ho*Wo output pixels
 // per image; 0 = the config cannot produce them (a tile would span more than GEN_TAY_IMG images).
 extern "C" int tp_conv_gen_tay_slots(int cfg, int HWo) {
   cfg &= ~(tp::CFG_SK | tp::CFG_SB);
@@ -1761,51 +1725,27 @@ extern "C" int tp_conv_gen_tay_slots(int cfg, int HWo) {
   return tp::gen_tay_slots(bm, HWo);
 }
 
-extern "C" hipError_t tp_conv_gen3(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, hipStream_t st) {
-  return tp_conv_gen4(x, w, B, H, W, Cin, Cout, ks, stride, pad, transposed, Ho_t, Wo_t, cfg, splits, scale, shift,
-                      relu, res, res_stride, mask, apoz, out, ws, bnpart, nullptr, 0, st);
-}
-
+// Full entry: ``transposed`` = data gradient of a strided conv (GEN 3) producing Ho_t x Wo_t
+// (the forward conv's input size); ``mask`` = ReLU-backward activation; ``res_stride``: see
+// ConvArgs. Forward convs pass transposed = 0 (Ho_t/Wo_t ignored), mask = null, res_stride = 1.
 // ``bnpart`` (nullable): [ceil(M / tile_m(cfg))][2][Cout] doubles receiving the per-tile column
 // sums / sums of squares of the output (training BatchNorm statistics); no split-K then.
 // ``tay_part`` (nullable, needs ``mask``, no split-K; 1x1 stride 1, or transposed 3x3 stride 2 at
 // even Ho / Wo): [R][B][Cout] Taylor partials, R = tp_conv_gen_tay_slots(cfg, Ho * Wo) (transposed:
 // 4 x tp_conv_gen_tay_slots(cfg, Ho * Wo / 4), one slot range per stride phase), every slot
 // written or left as the caller zeroed it.
-extern "C" hipError_t tp_conv_gen5(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, float* tay_part, int tay_mode, const uint8_t* res_bits,
-                                   const float* bnb_y, const float* bnb_mean, const float* bnb_invstd,
-                                   const uint8_t* bnb_bits, hipStream_t st);
-
-extern "C" hipError_t tp_conv_gen4(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, float* tay_part, int tay_mode, hipStream_t st) {
-  return tp_conv_gen5(x, w, B, H, W, Cin, Cout, ks, stride, pad, transposed, Ho_t, Wo_t, cfg, splits, scale, shift,
-                      relu, res, res_stride, mask, apoz, out, ws, bnpart, tay_part, tay_mode, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, st);
-}
-
 // ``res_bits`` (nullable; GEN 1, res at stride 1, no mask, Cout % 4 == 0): res is masked element-wise
 // by a ReLU bit mask (byte (pix * Cout + n) / 4, bit n % 4) before the add. ``bnb_y`` (nullable; GEN 1,
 // one K pass, with ``bnpart``): ``bnpart`` receives per M tile (sum gm, sum gm * (bnb_y - bnb_mean) *
 // bnb_invstd) of the stored gradient gm (masked by ``bnb_bits`` when given) instead of the output's
 // (sum, sum of squares): the backward statistics of the BatchNorm that produced the conv's input.
-extern "C" hipError_t tp_conv_gen5(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
-                                   int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
-                                   const float* scale, const float* shift, int relu, const float* res,
-                                   int res_stride, const float* mask, float* apoz, float* out, float* ws,
-                                   double* bnpart, float* tay_part, int tay_mode, const uint8_t* res_bits,
-                                   const float* bnb_y, const float* bnb_mean, const float* bnb_invstd,
-                                   const uint8_t* bnb_bits, hipStream_t st) {
+extern "C" hipError_t tp_conv_gen(const float* x, const float* w, int B, int H, int W, int Cin, int Cout, int ks,
+                                  int stride, int pad, int transposed, int Ho_t, int Wo_t, int cfg, int splits,
+                                  const float* scale, const float* shift, int relu, const float* res,
+                                  int res_stride, const float* mask, float* apoz, float* out, float* ws,
+                                  double* bnpart, float* tay_part, int tay_mode, const uint8_t* res_bits,
+                                  const float* bnb_y, const float* bnb_mean, const float* bnb_invstd,
+                                  const uint8_t* bnb_bits, hipStream_t st) {
   using namespace tp;
   const int gen = transposed ? 3 : (Cin == 4 ? 2 : 1);
   if ((gen != 2 && (Cin % 4 != 0 || Cin < 8)) || Cout % 4 != 0 || res_stride < 1) return hipErrorInvalidValue;

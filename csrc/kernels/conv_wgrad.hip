@@ -14,6 +14,7 @@
 // The pixel range is split over grid.y (split-K): partial slabs [split][Cout][Kpad] are summed
 // in a fixed order by wgrad_combine_par (deterministic, no atomics).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 
@@ -248,10 +249,10 @@ hipError_t launch_wgrad(const tp::WgradArgs& a, int splits, hipStream_t st) {
 // ks, ks) with element strides fs[4]; dw is then not written (may be null).
 // batch > 1: ``batch`` independent GEMMs (operands g + z*g_bstride, x + z*x_bstride) -> dw
 // [batch][Cout][Kpad]; no ``fin`` (the Winograd weight gradient's 16 transform-point GEMMs).
-extern "C" hipError_t tp_conv_wgrad3(const float* g, const float* x, float* dw, float* ws, int B, int H, int W,
-                                     int Cin, int Cout, int ks, int stride, int pad, int Kpad, int cfg, int splits,
-                                     float* fin, int fin_co, int fin_ci, const long long* fs, int batch,
-                                     long long g_bstride, long long x_bstride, hipStream_t st) {
+extern "C" hipError_t tp_conv_wgrad(const float* g, const float* x, float* dw, float* ws, int B, int H, int W,
+                                    int Cin, int Cout, int ks, int stride, int pad, int Kpad, int cfg, int splits,
+                                    float* fin, int fin_co, int fin_ci, const long long* fs, int batch,
+                                    long long g_bstride, long long x_bstride, hipStream_t st) {
   using namespace tp;
   if (Cin % 4 || Cout % 4 || Kpad % 32 || Kpad < ks * ks * Cin || splits < 1) return hipErrorInvalidValue;
   if (batch < 1 || batch > 65535 || (batch > 1 && fin)) return hipErrorInvalidValue;
@@ -317,18 +318,4 @@ extern "C" hipError_t tp_conv_wgrad3(const float* g, const float* x, float* dw, 
   else
     wgrad_combine_par<false><<<grid, 64 * sl, 0, st>>>(ws, a, dw, splits, n);
   return hipGetLastError();
-}
-
-extern "C" hipError_t tp_conv_wgrad2(const float* g, const float* x, float* dw, float* ws, int B, int H, int W,
-                                     int Cin, int Cout, int ks, int stride, int pad, int Kpad, int cfg, int splits,
-                                     float* fin, int fin_co, int fin_ci, const long long* fs, hipStream_t st) {
-  return tp_conv_wgrad3(g, x, dw, ws, B, H, W, Cin, Cout, ks, stride, pad, Kpad, cfg, splits, fin, fin_co, fin_ci, fs,
-                        1, 0, 0, st);
-}
-
-extern "C" hipError_t tp_conv_wgrad(const float* g, const float* x, float* dw, float* ws, int B, int H, int W,
-                                    int Cin, int Cout, int ks, int stride, int pad, int Kpad, int cfg, int splits,
-                                    hipStream_t st) {
-  return tp_conv_wgrad2(g, x, dw, ws, B, H, W, Cin, Cout, ks, stride, pad, Kpad, cfg, splits, nullptr, 0, 0, nullptr,
-                        st);
 }

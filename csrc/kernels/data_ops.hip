@@ -5,6 +5,7 @@
 // ToTensor + Normalize, writing the fp32 NCHW batch the model consumes. The reference runs
 // this per image on a host DataLoader worker (num_workers=1).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

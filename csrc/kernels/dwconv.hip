@@ -26,6 +26,7 @@
 // the parameter) and stores exact zeros in its padding lanes whatever the inputs hold there; the
 // weight gradient reduces and writes the channels below Cw only.
 #include "tp_dwconv.h"
+#include "tp_launchers.h"
 
 namespace tp {
 
@@ -331,8 +332,8 @@ static bool dw_carried_ok(int C, int Cw) { return Cw > 0 && Cw <= C && (Cw == C 
 
 // y = dwconv(x, w) (+ bias): x (B, H, W, C), w (Cw, 1, k, k), bias (Cw), y (B, Ho, Wo, C); the channels
 // c >= Cw of y are exact zeros, whatever x holds there
-extern "C" hipError_t tp_dwconv_fwd_cw(const float* x, const float* w, const float* bias, float* y, int B, int H,
-                                       int W, int C, int Cw, int k, int s, int pad, hipStream_t st) {
+extern "C" hipError_t tp_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H,
+                                    int W, int C, int Cw, int k, int s, int pad, hipStream_t st) {
   int Ho, Wo, cpr, nq;
   long long blocks;
   if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, x, w, bias, y))
@@ -350,14 +351,9 @@ extern "C" hipError_t tp_dwconv_fwd_cw(const float* x, const float* w, const flo
   return hipGetLastError();
 }
 
-extern "C" hipError_t tp_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W,
-                                    int C, int k, int s, int pad, hipStream_t st) {
-  return tp_dwconv_fwd_cw(x, w, bias, y, B, H, W, C, C, k, s, pad, st);
-}
-
 // dx (B, H, W, C) from g (B, Ho, Wo, C) and w (Cw, 1, k, k); the channels c >= Cw of dx are exact zeros
-extern "C" hipError_t tp_dwconv_dgrad_cw(const float* g, const float* w, float* dx, int B, int H, int W, int C, int Cw,
-                                         int k, int s, int pad, hipStream_t st) {
+extern "C" hipError_t tp_dwconv_dgrad(const float* g, const float* w, float* dx, int B, int H, int W, int C, int Cw,
+                                      int k, int s, int pad, hipStream_t st) {
   int Ho, Wo, cpr, nq;
   long long blocks;
   if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, w, dx))
@@ -382,11 +378,6 @@ extern "C" hipError_t tp_dwconv_dgrad_cw(const float* g, const float* w, float* 
   return hipGetLastError();
 }
 
-extern "C" hipError_t tp_dwconv_dgrad(const float* g, const float* w, float* dx, int B, int H, int W, int C, int k,
-                                      int s, int pad, hipStream_t st) {
-  return tp_dwconv_dgrad_cw(g, w, dx, B, H, W, C, C, k, s, pad, st);
-}
-
 // Chunks of the wgrad grid for P = B * Ho * Wo output pixels: about eight blocks per CU over the
 // (channel slices x chunks) grid, at least 256 pixels per chunk (a few strips per thread before the
 // block's LDS reduction), at most 1024 chunks. The workspace holds chunks * (k*k + 1) * C doubles.
@@ -401,9 +392,9 @@ extern "C" int tp_dwconv_wgrad_chunks(int P, int C) {
 // the Cw channels of the parameter and, with db, db[c] = sum g (Cw entries); g / x carry C >= Cw
 // channels per pixel. ws: tp_dwconv_wgrad_chunks(P, C) * (k*k + 1) * C doubles (sized by the carried
 // width), chunks = that count
-extern "C" hipError_t tp_dwconv_wgrad_cw(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
-                                         int B, int H, int W, int C, int Cw, int k, int s, int pad, long long s0,
-                                         long long s2, long long s3, hipStream_t st) {
+extern "C" hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
+                                      int B, int H, int W, int C, int Cw, int k, int s, int pad, long long s0,
+                                      long long s2, long long s3, hipStream_t st) {
   int Ho, Wo;
   if (!dw_carried_ok(C, Cw) || !tp::dw_geometry(B, H, W, C, k, s, pad, &Ho, &Wo) || !tp::dw_aligned(C, g, x, ws))
     return hipErrorInvalidValue;
@@ -430,10 +421,4 @@ extern "C" hipError_t tp_dwconv_wgrad_cw(const float* g, const float* x, float* 
   const int n = (k * k + 1) * C;
   tp::dwconv_wgrad_fold<<<tp::ceil_div(n, 16), 256, 0, st>>>(ws, dw, db, chunks, C, k, s0, s2, s3, Cw);
   return hipGetLastError();
-}
-
-extern "C" hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks,
-                                      int B, int H, int W, int C, int k, int s, int pad, long long s0, long long s2,
-                                      long long s3, hipStream_t st) {
-  return tp_dwconv_wgrad_cw(g, x, dw, db, ws, chunks, B, H, W, C, C, k, s, pad, s0, s2, s3, st);
 }

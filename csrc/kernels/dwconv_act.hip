@@ -27,6 +27,7 @@
 // channels of its slot) and sums the slots. APoZ counts are integers, added with float atomics
 // after the same block reduction (exact and order independent up to 2^24).
 #include "tp_dwconv.h"
+#include "tp_launchers.h"
 
 #include <initializer_list>
 

@@ -21,6 +21,7 @@
 // slower on narrow feature maps.) The order of the subtractions is the sequential one above for every
 // element: no atomics, the same bits on every run.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

@@ -8,6 +8,7 @@
 //                    along an axis with a shared keep-index list (pruner.py:106-112,
 //                    opt_pruner.py:17-19 issue one ATen index_select per tensor).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

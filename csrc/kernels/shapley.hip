@@ -7,6 +7,7 @@
 // given their masks, so K prefixes are materialised in a single launch as a (K*B)
 // batch (prefix_mask) and the K deltas are scattered on device (shapley_accumulate).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

@@ -19,6 +19,7 @@
 // batches, narrow layers) the pixels of an image are split over `splits` blocks which write
 // partial slots [split][b][c], folded in slot order by a second small kernel.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

@@ -4,6 +4,7 @@
 // not depend on the launch geometry. y = x * (keep ? 1/(1-p) : 0) as a multiplication, so NaN
 // inputs stay NaN even in dropped positions (the pruner's NaN probe relies on NaN propagation).
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

@@ -17,6 +17,7 @@
 // channels_last parameter is read in place, no contiguous copy); a flat element space over the
 // operands (start = chunk-aligned prefix offset), one descriptor search per 4096-element chunk.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 

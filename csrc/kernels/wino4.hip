@@ -27,6 +27,7 @@
 // Transform points 0, +-1, +-2, inf (Lavin & Gray); fp32 error ~2e-6 relative (64-channel
 // reduction), well inside the engine's fp64-oracle tolerances.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1218,7 +1219,7 @@ static int kernel_mode() {
 }  // namespace tp
 
 // U images of a 3x3 weight for wino4: (C/8, K/32, 9216) floats. w: (S0, S1, 3, 3) = the forward
-// weight (Cout, Cin, 3, 3), possibly narrower than the padded GEMM; flip_t as tp_wino_weights2.
+// weight (Cout, Cin, 3, 3), possibly narrower than the padded GEMM; flip_t as tp_wino_weights.
 // strides: w's element strides (st0, st1, st2, st3) — (S1*9, 9, 3, 1) when contiguous
 extern "C" hipError_t tp_wino4_weights_strided(const float* w, float* u, int K, int C, int flip_t, int S0, int S1,
                                                long long st0, long long st1, int st2, int st3, hipStream_t st) {
@@ -1275,21 +1276,16 @@ extern "C" int tp_wino4_taylor_slots(int S) {
 // splits > 1 (MODE 2/3): the channel chunks are split over gridDim.y blocks that write raw slabs
 // into ws (splits x M x K floats; pooled row order for epi 1), combined in a fixed order by the
 // shared split-K epilogue (conv_mfma.hip) — small batches get enough blocks to fill the chip.
-extern "C" hipError_t tp_conv_epilogue_slabs(const float* ws, int splits, int B, int H, int W, int K, int epi,
-                                              const float* scale, const float* shift, int relu, float* out,
-                                              uint8_t* out_argmax, const float* act, float* taylor,
-                                              float* apoz, int tay_mode, hipStream_t st);
-
 // variant 0: the TP_W4_MODE kernel (default MODE 3); variant 2: MODE 3 with spread U DMA;
 // variant 3: MODE 3 with split points (each wave 18 points x 32 outputs, half the transform).
 // ko (0 = K): output channels stored per pixel (K rounded down to them: ko % 4 == 0, K - 32 < ko <=
 // K): the U images and the MFMAs cover K = ko rounded up to 32, the outputs, activations, BN
 // scale / shift, Taylor / APoZ slabs have ko channels — pruned widths stay unpadded in HBM.
-extern "C" hipError_t tp_conv_wino4_ko(const float* x, const float* u, int B, int S, int C, int K, int epi,
-                                       const float* scale, const float* shift, int relu, float* out,
-                                       uint8_t* out_argmax, const float* act, float* taylor, float* apoz, int tay_mode,
-                                       int splits, float* ws, int variant, hipStream_t st, const uint8_t* unpool_am,
-                                       int ko) {
+extern "C" hipError_t tp_conv_wino4(const float* x, const float* u, int B, int S, int C, int K, int epi,
+                                    const float* scale, const float* shift, int relu, float* out,
+                                    uint8_t* out_argmax, const float* act, float* taylor, float* apoz, int tay_mode,
+                                    int splits, float* ws, int variant, hipStream_t st, const uint8_t* unpool_am,
+                                    int ko) {
   using namespace tp::w4;
   if (!tp_wino4_ok(S, S, C, K) || B <= 0) return hipErrorInvalidValue;
   if (ko == 0) ko = K;
@@ -1414,14 +1410,6 @@ extern "C" hipError_t tp_conv_wino4_ko(const float* x, const float* u, int B, in
 #undef TP_W4S
 #undef TP_W4
   return hipGetLastError();
-}
-
-extern "C" hipError_t tp_conv_wino4(const float* x, const float* u, int B, int S, int C, int K, int epi,
-                                    const float* scale, const float* shift, int relu, float* out, uint8_t* out_argmax,
-                                    const float* act, float* taylor, float* apoz, int tay_mode, int splits,
-                                    float* ws, int variant, hipStream_t st, const uint8_t* unpool_am) {
-  return tp_conv_wino4_ko(x, u, B, S, C, K, epi, scale, shift, relu, out, out_argmax, act, taylor, apoz, tay_mode,
-                          splits, ws, variant, st, unpool_am, K);
 }
 
 // static LDS bytes of a wino4 instantiation (occupancy / budget guard)

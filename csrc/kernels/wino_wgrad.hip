@@ -13,6 +13,7 @@
 // Pays off where the GEMM dominates the extra transform traffic (C >= 128); the training conv's
 // tuner times it against the direct wgrad per shape.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 namespace tp {
 
@@ -126,11 +127,6 @@ __global__ __launch_bounds__(256) void wgrad_out_transform(const float* __restri
 
 }  // namespace tp
 
-extern "C" hipError_t tp_conv_wgrad3(const float* g, const float* x, float* dw, float* ws, int B, int H, int W,
-                                     int Cin, int Cout, int ks, int stride, int pad, int Kpad, int cfg, int splits,
-                                     float* fin, int fin_co, int fin_ci, const long long* fs, int batch,
-                                     long long g_bstride, long long x_bstride, hipStream_t st);
-
 // Workspace (floats) of tp_wino_wgrad: V (16*T*Cin) + dM (16*T*Cout) + dU (16*Cout*Kp) + the
 // split slabs of the batched GEMM (splits*16*Cout*Kp); Kp = Cin rounded up to the GEMM's 32-wide
 // K granule (pruned widths: the padded columns of dU are zeros nobody reads).
@@ -166,8 +162,8 @@ extern "C" hipError_t tp_wino_wgrad(const float* g, const float* x, float* ws, i
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // 16 GEMMs dU[xi] = dM[xi]^T V[xi] over the T tiles: "1x1 conv" weight gradients of (1, T, 1, C)
-  e = tp_conv_wgrad3(m, v, du, splits > 1 ? slabs : nullptr, 1, (int)T, 1, Cin, Cout, 1, 1, 0, Kp, cfg, splits,
-                     nullptr, 0, 0, nullptr, 16, T * Cout, T * Cin, st);
+  e = tp_conv_wgrad(m, v, du, splits > 1 ? slabs : nullptr, 1, (int)T, 1, Cin, Cout, 1, 1, 0, Kp, cfg, splits,
+                    nullptr, 0, 0, nullptr, 16, T * Cout, T * Cin, st);
   if (e != hipSuccess) return e;
   grid = (unsigned)std::min<long long>(ceil_div((long long)fin_co * fin_ci, 256), 16384);
   wgrad_out_transform<<<grid, 256, 0, st>>>(du, fin, Cout, Kp, fin_co, fin_ci, fs[0], fs[1], fs[2], fs[3]);

@@ -29,6 +29,7 @@
 //     max-pool window, so pooling is 3 max ops on values the lane already holds; BN affine,
 //     ReLU, Taylor partials and the masked gradient are fused exactly as in conv_mfma.hip.
 #include "tp_common.h"
+#include "tp_launchers.h"
 
 #include <cstdlib>
 #include <map>
@@ -1154,23 +1155,13 @@ static SpanGeom span_geometry(int H, int W) {
 
 }  // namespace tp
 
-// Winograd conv: same operand/epilogue contract as tp_conv_igemm (3x3, stride 1, pad 1),
-// ``u`` = U images from winograd_weights(). epi: 0 fwd, 1 fwd+pool, 2 bwd (dgrad epilogue).
-// H, W even, C % 8 == 0, K % 32 == 0. splits > 1 -> partial slabs in ``ws`` + combine.
-// staged: bit 0 = LDS-staged input region when the shape allows it (else direct loads); bit 1 =
-// ``u`` holds bf16 images (tp_wino_weights_bf16) for the BF kernels — staged input modes only.
-extern "C" hipError_t tp_conv_epilogue_slabs(const float* ws, int splits, int B, int H, int W, int K, int epi,
-                                              const float* scale, const float* shift, int relu, float* out,
-                                              uint8_t* out_argmax, const float* act, float* taylor,
-                                              float* apoz, int tay_mode, hipStream_t st);
-
 extern "C" int tp_wino_taylor_slots(int H, int W) { return tp::wino_taylor_slots(H, W); }
 
 // w: (S0, S1, 3, 3) = the forward weight (Cout, Cin, 3, 3), possibly narrower than the padded
 // GEMM: flip_t = 0 -> U of (K = Cout_p, C = Cin_p); flip_t = 1 -> the dgrad operand, (K = Cin_p,
 // C = Cout_p) with rotated taps. u: (C/8, K/32, 4096) images. K % 32 == 0, C % 8 == 0.
-extern "C" hipError_t tp_wino_weights2(const float* w, float* u, int K, int C, int flip_t, int S0, int S1,
-                                       hipStream_t st) {
+extern "C" hipError_t tp_wino_weights(const float* w, float* u, int K, int C, int flip_t, int S0, int S1,
+                                      hipStream_t st) {
   if (K % 32 || C % 8 || K <= 0 || C <= 0 || S0 <= 0 || S1 <= 0) return hipErrorInvalidValue;
   if (flip_t ? (S0 > C || S1 > K) : (S0 > K || S1 > C)) return hipErrorInvalidValue;
   const long long total = (long long)(C / 8) * (K / 32) * tp::W_UIMG;
@@ -1188,11 +1179,6 @@ extern "C" hipError_t tp_wino_weights_bf16(const float* w, void* u, int K, int C
   const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 16384);
   tp::wino_weight_transform_bf16<<<grid, 256, 0, st>>>(w, static_cast<unsigned*>(u), K, C, flip_t, S0, S1);
   return hipGetLastError();
-}
-
-// w padded to the GEMM: (K, C, 3, 3) (flip_t = 0) or (C, K, 3, 3) (flip_t = 1)
-extern "C" hipError_t tp_wino_weights(const float* w, float* u, int K, int C, int flip_t, hipStream_t st) {
-  return tp_wino_weights2(w, u, K, C, flip_t, flip_t ? C : K, flip_t ? K : C, st);
 }
 
 // static LDS bytes of the largest Winograd kernel instantiations (occupancy guard)
@@ -1223,6 +1209,11 @@ extern "C" void tp_wino_geometry(int H, int W, int unpool, int* out9) {
   for (int i = 0; i < 9; ++i) out9[i] = vals[i];
 }
 
+// Winograd conv: same operand/epilogue contract as tp_conv_igemm (3x3, stride 1, pad 1),
+// ``u`` = U images from winograd_weights(). epi: 0 fwd, 1 fwd+pool, 2 bwd (dgrad epilogue).
+// H, W even, C % 8 == 0, K % 32 == 0. splits > 1 -> partial slabs in ``ws`` + combine.
+// staged: bit 0 = LDS-staged input region when the shape allows it (else direct loads); bit 1 =
+// ``u`` holds bf16 images (tp_wino_weights_bf16) for the BF kernels — staged input modes only.
 extern "C" hipError_t tp_conv_wino(const float* x, const uint8_t* x_argmax, const float* u, int B, int H, int W,
                                    int C, int K, int unpool, int epi, int splits, int staged, const float* scale,
                                    const float* shift, int relu, float* out, uint8_t* out_argmax, const float* act,

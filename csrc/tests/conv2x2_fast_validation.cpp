@@ -10,16 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "tp_expect.h"
 #include "tp_launchers.h"
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
 
 static float* const A16 = reinterpret_cast<float*>(64);  // aligned, never dereferenced
 static float* const A4 = reinterpret_cast<float*>(68);   // 4-byte aligned only

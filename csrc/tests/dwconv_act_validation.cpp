@@ -9,24 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" {
-hipError_t tp_dwconv_act_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
-                             float* apoz, int B, int H, int W, int C, int k, int s, int pad, int in_act, int out_act,
-                             hipStream_t st);
-int tp_dwconv_act_tay_slots(int H, int W, int C);
-hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
-                               float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
-                               int pad, int in_act, int out_act, hipStream_t st);
-}
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
+#include "tp_expect.h"
+#include "tp_launchers.h"
 
 static float* const A16 = reinterpret_cast<float*>(64);  // aligned, never dereferenced
 static float* const A4 = reinterpret_cast<float*>(68);

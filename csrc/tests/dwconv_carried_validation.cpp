@@ -1,4 +1,4 @@
-// Host-side validation of the carried-width depthwise-conv launchers (tp_dwconv_*_cw,
+// Host-side validation of the carried-width depthwise-conv launchers (tp_dwconv_* at Cw < C,
 // csrc/kernels/dwconv.hip) and of the BatchNorm launchers' activation code (batchnorm.hip), built
 // with AddressSanitizer + UBSan on the host code like dwconv_validation.cpp. A carried width has
 // the activations at C channels per pixel and the parameter at Cw <= C; the launchers must reject,
@@ -13,30 +13,8 @@
 #include <cstdlib>
 #include <initializer_list>
 
+#include "tp_expect.h"
 #include "tp_launchers.h"
-
-extern "C" {
-hipError_t tp_bn_fwd_train5(const float* x, float* y, int P, int C, int Cr, const float* gamma, const float* beta,
-                            float eps, float momentum, float* run_mean, float* run_var, float* mean, float* invstd,
-                            float* a, float* b, double* ws, const float* res, int relu, uint8_t* mko, long long* nbt,
-                            hipStream_t st);
-hipError_t tp_bn_fwd_train_pre2(const float* x, float* y, int P, int C, int Cr, const float* gamma, const float* beta,
-                                float eps, float momentum, float* run_mean, float* run_var, float* mean, float* invstd,
-                                float* a, float* b, double* ws, const double* pre, int G, const float* res, int relu,
-                                uint8_t* mko, long long* nbt, hipStream_t st);
-hipError_t tp_bn_fwd_train2(const float* x, float* y, int P, int C, const float* gamma, const float* beta, float eps,
-                            float momentum, float* run_mean, float* run_var, float* mean, float* invstd, float* a,
-                            float* b, double* ws, const float* res, int relu, hipStream_t st);
-}
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
 
 // the three launchers on one geometry (null operands: never touched when the call is rejected)
 static bool all_reject(int B, int H, int W, int C, int Cw, int k, int s, int pad) {
@@ -44,10 +22,10 @@ static bool all_reject(int B, int H, int W, int C, int Cw, int k, int s, int pad
   double* ws = reinterpret_cast<double*>(16);
   float* dw = reinterpret_cast<float*>(16);
   const int P = B > 0 && H > 0 && W > 0 ? 1 : 0;  // (any chunk count: the width is checked first)
-  const bool f = tp_dwconv_fwd_cw(n, n, n, n, B, H, W, C, Cw, k, s, pad, nullptr) == hipErrorInvalidValue;
-  const bool d = tp_dwconv_dgrad_cw(n, n, n, B, H, W, C, Cw, k, s, pad, nullptr) == hipErrorInvalidValue;
-  const bool g = tp_dwconv_wgrad_cw(n, n, dw, n, ws, tp_dwconv_wgrad_chunks(P, C), B, H, W, C, Cw, k, s, pad,
-                                    (long long)k * k, k, 1, nullptr) == hipErrorInvalidValue;
+  const bool f = tp_dwconv_fwd(n, n, n, n, B, H, W, C, Cw, k, s, pad, nullptr) == hipErrorInvalidValue;
+  const bool d = tp_dwconv_dgrad(n, n, n, B, H, W, C, Cw, k, s, pad, nullptr) == hipErrorInvalidValue;
+  const bool g = tp_dwconv_wgrad(n, n, dw, n, ws, tp_dwconv_wgrad_chunks(P, C), B, H, W, C, Cw, k, s, pad,
+                                 (long long)k * k, k, 1, nullptr) == hipErrorInvalidValue;
   return f && d && g;
 }
 
@@ -72,54 +50,54 @@ int main() {
   EXPECT(all_reject(2147483647, 2147483647, 2147483647, 2147483644, 5, 3, 1, 1));
   // more 256-thread blocks than a grid takes: millions of rows (forward / dgrad), millions of channels (the fold)
   float* n = nullptr;
-  EXPECT(tp_dwconv_fwd_cw(n, n, n, n, 1 << 12, 1 << 13, 1, 4, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad_cw(n, n, n, 1 << 12, 1 << 13, 1, 4, 3, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad_cw(n, n, reinterpret_cast<float*>(16), n, reinterpret_cast<double*>(16),
-                            tp_dwconv_wgrad_chunks(1, 1 << 25), 1, 1, 1, 1 << 25, 5, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_fwd(n, n, n, n, 1 << 12, 1 << 13, 1, 4, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(n, n, n, 1 << 12, 1 << 13, 1, 4, 3, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(n, n, reinterpret_cast<float*>(16), n, reinterpret_cast<double*>(16),
+                         tp_dwconv_wgrad_chunks(1, 1 << 25), 1, 1, 1, 1 << 25, 5, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
   // misaligned pointers: a carried width always runs float4 accesses (16-byte alignment)
   const float* a4 = reinterpret_cast<const float*>(4);
   float* a16 = reinterpret_cast<float*>(16);
   double* ws = reinterpret_cast<double*>(16);
-  EXPECT(tp_dwconv_fwd_cw(a4, a16, n, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd_cw(a16, a4, n, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd_cw(a16, a16, a4, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd_cw(a16, a16, n, const_cast<float*>(a4), 2, 8, 8, 16, 13, 3, 1, 1, nullptr) ==
+  EXPECT(tp_dwconv_fwd(a4, a16, n, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a4, n, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a16, a4, a16, 2, 8, 8, 16, 13, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a16, n, const_cast<float*>(a4), 2, 8, 8, 16, 13, 3, 1, 1, nullptr) ==
          hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad_cw(a4, a16, a16, 2, 8, 8, 16, 13, 5, 2, 2, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad_cw(a16, a4, a16, 2, 8, 8, 16, 13, 5, 2, 2, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad_cw(a16, a16, const_cast<float*>(a4), 2, 8, 8, 16, 13, 5, 2, 2, nullptr) ==
+  EXPECT(tp_dwconv_dgrad(a4, a16, a16, 2, 8, 8, 16, 13, 5, 2, 2, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(a16, a4, a16, 2, 8, 8, 16, 13, 5, 2, 2, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(a16, a16, const_cast<float*>(a4), 2, 8, 8, 16, 13, 5, 2, 2, nullptr) ==
          hipErrorInvalidValue);
   const int ch = tp_dwconv_wgrad_chunks(2 * 8 * 8, 16);
-  EXPECT(tp_dwconv_wgrad_cw(a4, a16, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a4, a16, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad_cw(a16, a4, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a4, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad_cw(a16, a16, a16, n, reinterpret_cast<double*>(72), ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1,
-                            nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad_cw(a16, a16, n, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, reinterpret_cast<double*>(72), ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1,
+                         nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a16, n, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);  // no dw
-  EXPECT(tp_dwconv_wgrad_cw(a16, a16, a16, n, ws, ch + 1, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch + 1, 2, 8, 8, 16, 13, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);  // the workspace is sized by the carried width's chunk count
-  EXPECT(tp_dwconv_wgrad_cw(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 1ll << 40, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 13, 3, 1, 1, 1ll << 40, 3, 1, nullptr) ==
          hipErrorInvalidValue);  // a dW stride past the 32-bit range
 
   // BatchNorm forward: activation codes 0 (none), 1 (ReLU), 2 (ReLU6, with a mask to write) only
   uint8_t* mk = reinterpret_cast<uint8_t*>(16);
   for (int bad : {-1, 3, 4, 256, -2147483647 - 1, 2147483647}) {
-    EXPECT(tp_bn_fwd_train5(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, bad, mk, nullptr,
-                            nullptr) == hipErrorInvalidValue);
-    EXPECT(tp_bn_fwd_train_pre2(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, nullptr, 1, n, bad, mk,
-                                nullptr, nullptr) == hipErrorInvalidValue);
-    EXPECT(tp_bn_fwd_train2(n, n, 64, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, bad, nullptr) ==
-           hipErrorInvalidValue);
+    EXPECT(tp_bn_fwd_train(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, bad, mk, nullptr,
+                           nullptr) == hipErrorInvalidValue);
+    EXPECT(tp_bn_fwd_train_pre(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, nullptr, 1, n, bad, mk,
+                               nullptr, nullptr) == hipErrorInvalidValue);
+    EXPECT(tp_bn_fwd_train(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, bad, nullptr, nullptr,
+                           nullptr) == hipErrorInvalidValue);
   }
-  EXPECT(tp_bn_fwd_train5(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, 2, nullptr, nullptr,
-                          nullptr) == hipErrorInvalidValue);  // ReLU6 without a mask
-  EXPECT(tp_bn_fwd_train_pre2(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, nullptr, 1, n, 2,
-                              nullptr, nullptr, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_bn_fwd_train2(n, n, 64, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, 2, nullptr) ==
-         hipErrorInvalidValue);  // (the mask-free entry points cannot run ReLU6)
+  EXPECT(tp_bn_fwd_train(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, 2, nullptr, nullptr,
+                         nullptr) == hipErrorInvalidValue);  // ReLU6 without a mask
+  EXPECT(tp_bn_fwd_train_pre(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, nullptr, 1, n, 2, nullptr,
+                             nullptr, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_bn_fwd_train(n, n, 64, 8, 8, n, n, 1e-5f, 0.1f, n, n, n, n, n, n, nullptr, n, 2, nullptr, nullptr,
+                         nullptr) == hipErrorInvalidValue);  // (the mask-free entry points cannot run ReLU6)
 
   if (failures) {
     std::fprintf(stderr, "%d failure(s)\n", failures);

@@ -9,34 +9,17 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" {
-hipError_t tp_dwconv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C,
-                         int k, int s, int pad, hipStream_t st);
-hipError_t tp_dwconv_dgrad(const float* g, const float* w, float* dx, int B, int H, int W, int C, int k, int s,
-                           int pad, hipStream_t st);
-int tp_dwconv_wgrad_chunks(int P, int C);
-hipError_t tp_dwconv_wgrad(const float* g, const float* x, float* dw, float* db, double* ws, int chunks, int B, int H,
-                           int W, int C, int k, int s, int pad, long long s0, long long s2, long long s3,
-                           hipStream_t st);
-}
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
+#include "tp_expect.h"
+#include "tp_launchers.h"
 
 // the three launchers on one geometry (null operands: never touched when the call is rejected)
 static bool all_reject(int B, int H, int W, int C, int k, int s, int pad) {
   float* n = nullptr;
   double* ws = reinterpret_cast<double*>(16);
   float* dw = reinterpret_cast<float*>(16);
-  const bool f = tp_dwconv_fwd(n, n, n, n, B, H, W, C, k, s, pad, nullptr) == hipErrorInvalidValue;
-  const bool d = tp_dwconv_dgrad(n, n, n, B, H, W, C, k, s, pad, nullptr) == hipErrorInvalidValue;
-  const bool g = tp_dwconv_wgrad(n, n, dw, n, ws, 1, B, H, W, C, k, s, pad, (long long)k * k, k, 1, nullptr) ==
+  const bool f = tp_dwconv_fwd(n, n, n, n, B, H, W, C, C, k, s, pad, nullptr) == hipErrorInvalidValue;
+  const bool d = tp_dwconv_dgrad(n, n, n, B, H, W, C, C, k, s, pad, nullptr) == hipErrorInvalidValue;
+  const bool g = tp_dwconv_wgrad(n, n, dw, n, ws, 1, B, H, W, C, C, k, s, pad, (long long)k * k, k, 1, nullptr) ==
                  hipErrorInvalidValue;
   return f && d && g;
 }
@@ -69,36 +52,37 @@ int main() {
   // shapes that fit in 2^31 bytes but would need more 256-thread blocks than a grid takes (2^32
   // threads): millions of rows of one element (forward / dgrad), millions of channels (the fold)
   float* n = nullptr;
-  EXPECT(tp_dwconv_fwd(n, n, n, n, 1 << 12, 1 << 13, 1, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad(n, n, n, 1 << 12, 1 << 13, 1, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(n, n, n, n, 1 << 12, 1 << 13, 1, 1, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(n, n, n, 1 << 12, 1 << 13, 1, 1, 1, 3, 1, 1, nullptr) == hipErrorInvalidValue);
   EXPECT(tp_dwconv_wgrad(n, n, reinterpret_cast<float*>(16), n, reinterpret_cast<double*>(16),
-                         tp_dwconv_wgrad_chunks(1, 1 << 25), 1, 1, 1, 1 << 25, 3, 1, 1, 9, 3, 1, nullptr) ==
+                         tp_dwconv_wgrad_chunks(1, 1 << 25), 1, 1, 1, 1 << 25, 1 << 25, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
   // misaligned pointers on the float4 path (C % 4 == 0), one operand at a time
   float* a16 = reinterpret_cast<float*>(64);
   float* a4 = reinterpret_cast<float*>(68);
   double* ws = reinterpret_cast<double*>(64);
-  EXPECT(tp_dwconv_fwd(a4, a16, n, a16, 2, 8, 8, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd(a16, a4, n, a16, 2, 8, 8, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd(a16, a16, a4, a16, 2, 8, 8, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_fwd(a16, a16, n, a4, 2, 8, 8, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad(a4, a16, a16, 2, 8, 8, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad(a16, a4, a16, 2, 8, 8, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_dgrad(a16, a16, a4, 2, 8, 8, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a4, a16, n, a16, 2, 8, 8, 16, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a4, n, a16, 2, 8, 8, 16, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a16, a4, a16, 2, 8, 8, 16, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_fwd(a16, a16, n, a4, 2, 8, 8, 16, 16, 3, 1, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(a4, a16, a16, 2, 8, 8, 16, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(a16, a4, a16, 2, 8, 8, 16, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_dgrad(a16, a16, a4, 2, 8, 8, 16, 16, 5, 2, 2, nullptr) == hipErrorInvalidValue);
   const int ch = tp_dwconv_wgrad_chunks(2 * 8 * 8, 16);
-  EXPECT(tp_dwconv_wgrad(a4, a16, a16, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a4, a16, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, reinterpret_cast<double*>(72), ch, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1,
+  EXPECT(tp_dwconv_wgrad(a4, a16, a16, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a4, a16, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, reinterpret_cast<double*>(72), ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1,
                          nullptr) == hipErrorInvalidValue);
   // wgrad: missing outputs / workspace, a chunk count that is not the helper's, bad dW strides
-  EXPECT(tp_dwconv_wgrad(a16, a16, n, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, nullptr, ch, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, n, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, nullptr, ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch + 1, 2, 8, 8, 16, 3, 1, 1, 9, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch + 1, 2, 8, 8, 16, 16, 3, 1, 1, 9, 3, 1, nullptr) ==
          hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 0, 3, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 9, -3, 1, nullptr) == hipErrorInvalidValue);
-  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 3, 1, 1, 1ll << 40, 3, 1, nullptr) ==
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 0, 3, 1, nullptr) == hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 9, -3, 1, nullptr) ==
+         hipErrorInvalidValue);
+  EXPECT(tp_dwconv_wgrad(a16, a16, a16, n, ws, ch, 2, 8, 8, 16, 16, 3, 1, 1, 1ll << 40, 3, 1, nullptr) ==
          hipErrorInvalidValue);
 
   // workspace chunks: at least one, never more than the pixels allow, the workspace below 2^31 bytes

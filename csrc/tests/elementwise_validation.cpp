@@ -13,55 +13,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" {
-hipError_t tp_channel_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C, int S,
-                             int mode, int channels_last, hipStream_t st);
-int tp_channel_reduce_ws_elems(int B, int C, int S, int channels_last);
-int tp_channel_reduce_chunks(int B, int C, int S, int vec);
-hipError_t tp_column_accumulate(const float* v, double* acc_sum, double* acc_sq, int B, int C, hipStream_t st);
-int tp_score_fold_ws_elems(const int* B, const int* C, int count);
-hipError_t tp_score_fold_multi(float* const* T, double* const* acc, const int* B, const int* C, const int* R,
-                               int count, int take_abs, int after, double* ws, hipStream_t st);
-hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx, int nidx, float value,
-                           hipStream_t st);
-hipError_t tp_nan_channels(const float* x, long long B, int C, long long S, uint8_t* flags, hipStream_t st);
-hipError_t tp_gather_multi(const void* const* srcs, void* const* dsts, const long long* outer, const long long* n,
-                           const long long* inner, int count, int elsize, const int64_t* keep, long long nkeep,
-                           hipStream_t st);
-hipError_t tp_maxpool2_nhwc(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, hipStream_t st);
-hipError_t tp_unpool2_nhwc(const float* g, const uint8_t* am, float* out, int B, int H, int W, int C, hipStream_t st);
-hipError_t tp_maxpool_nhwc(const float* x, float* y, int B, int H, int W, int C, int k, int s, int pad,
-                           hipStream_t st);
-hipError_t tp_avgpool_nhwc(const float* x, float* y, int B, int HW, int C, hipStream_t st);
-hipError_t tp_prefix_mask(const float* z, float* out, const int* rank, long long N, int C, int S, int channels_last,
-                          int p0, int K, hipStream_t st);
-hipError_t tp_shapley_scatter(const float* L, const int* perm, double* sv, int row0, int B, int n, int k0, int K,
-                              double scale, hipStream_t st);
-hipError_t tp_shapley_column(const float* L, const int* perm, double* sv_col, int B, int k0, int K, double scale,
-                             hipStream_t st);
-hipError_t tp_cross_entropy(const float* logits, const int64_t* target, float* loss, float* grad, int B, int NC,
-                            float gscale, hipStream_t st);
-hipError_t tp_prefix_tri_operands(const float* z, const float* W, const int* perm, int B, int C, int N, int p0,
-                                  int cnt, int Kc, float* T, float* Wsub, hipStream_t st);
-void tp_philox4x32(unsigned long long ctr, unsigned long long key, unsigned* out);
-hipError_t tp_dropout(const float* x, float* y, long long n, unsigned long long seed, double p, hipStream_t st);
-hipError_t tp_maxpool_fwd_arg(const float* x, float* y, uint8_t* am, int B, int H, int W, int C, int k, int s, int pad,
-                              hipStream_t st);
-hipError_t tp_maxpool_bwd(const float* g, const uint8_t* am, float* dx, int B, int H, int W, int C, int k, int s,
-                          int pad, hipStream_t st);
-hipError_t tp_avgpool_bwd(const float* g, float* dx, int B, int HW, int C, hipStream_t st);
-hipError_t tp_augment_u8(const uint8_t* src, const int64_t* idx, const int* aug, int B, int C, int H, int W, int pad,
-                         const float* mean, const float* inv_std, float* out, hipStream_t st);
-}
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
+#include "tp_expect.h"
+#include "tp_launchers.h"
 
 static float* const A16 = reinterpret_cast<float*>(64);  // aligned stand-ins: never dereferenced
 static float* const A4 = reinterpret_cast<float*>(68);   // 4-byte aligned only

@@ -9,18 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt,
-                                        const int* perm, float* out, int N, int C, int Co, int n, int p0, int cnt,
-                                        hipStream_t st);
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
+#include "tp_expect.h"
+#include "tp_launchers.h"
 
 static float* const A16 = reinterpret_cast<float*>(64);  // aligned, never dereferenced
 static float* const A4 = reinterpret_cast<float*>(68);   // 4-byte aligned only

@@ -9,30 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-extern "C" {
-int tp_se_splits(int B, int HW, int C);
-hipError_t tp_se_pool(const float* x, float* p, float* ws, int splits, int B, int HW, int C, hipStream_t st);
-hipError_t tp_se_gate_fwd(const float* p, const float* w1, const float* b1, const float* w2, const float* b2,
-                          float* h, float* s, int B, int C, int Cs, int gate, hipStream_t st);
-hipError_t tp_se_scale(const float* x, const float* s, float* out, int B, int HW, int C, hipStream_t st);
-hipError_t tp_se_bwd_reduce(const float* g, const float* x, float* ds, float* ws, int splits, int B, int HW, int C,
-                            hipStream_t st);
-hipError_t tp_se_gate_bwd(const float* ds, const float* s, const float* h, const float* w1, const float* w2,
-                          float* dz2, float* dz1, float* dp, int B, int C, int Cs, int gate, hipStream_t st);
-hipError_t tp_se_bwd_dx(const float* g, const float* s, const float* dp, float* dx, int B, int HW, int C,
-                        hipStream_t st);
-hipError_t tp_se_wgrad(const float* a, const float* m, float* dw, float* db, int B, int R, int K, long long s0,
-                       long long s1, hipStream_t st);
-}
-
-static int failures = 0;
-#define EXPECT(cond)                                                   \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      std::fprintf(stderr, "%s:%d: EXPECT(%s) failed\n", __FILE__, __LINE__, #cond); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
+#include "tp_expect.h"
+#include "tp_launchers.h"
 
 static float* const A16 = reinterpret_cast<float*>(64);  // aligned stand-ins: never dereferenced
 static float* const A4 = reinterpret_cast<float*>(68);   // 4-byte aligned only

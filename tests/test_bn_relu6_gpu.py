@@ -142,7 +142,7 @@ def test_relu6_rejections(cuda):
             T.bn_train_bwd(gh, xh, gamma.to(cuda), mean, invstd, True, None, False, mk, 13, None, bad)
     # a ReLU6 forward asked not to return a mask: the op always returns one, so this can only be
     # asked of the launcher, which refuses before it looks at any pointer (hipErrorInvalidValue = 1)
-    fwd = ctypes.CDLL(str(_LIB)).tp_bn_fwd_train5
+    fwd = ctypes.CDLL(str(_LIB)).tp_bn_fwd_train
     ptr, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     fwd.argtypes = [ptr, ptr, i32, i32, i32, ptr, ptr, f32, f32] + [ptr] * 8 + [i32, ptr, ptr, ptr]
     fwd.restype = i32

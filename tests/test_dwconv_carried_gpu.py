@@ -1,5 +1,5 @@
 """Depthwise-conv kernels on carried (padded) widths: the activations hold Cp >= Cw channels per
-pixel, the parameter Cw (csrc/kernels/dwconv.hip, the CARRY kernels behind tp_dwconv_*_cw).
+pixel, the parameter Cw (csrc/kernels/dwconv.hip, the CARRY kernels behind tp_dwconv_* at Cw < C).
 
 The real channels are checked against the fp64 references of tests/test_dwconv_gpu.py with its
 derived bounds (fp32 accumulation of n terms: error <= n * 2^-24 * sum|terms|; see that file). The

@@ -13,8 +13,8 @@ import pytest
 
 @pytest.mark.skipif(not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), reason="needs hipcc")
 def test_prefix_project_validation_asan():
-    from torchpruner_amd._build import build_prefix_project_sanitizer
-    exe = build_prefix_project_sanitizer()
+    from torchpruner_amd._build import build_host_program
+    exe = build_host_program("prefix_project_validation")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -12,6 +12,11 @@ Design
 * Everything is linked with ``-shared`` into ``torchpruner_amd/_C.so`` against the
   HIP runtime that ships inside torch (same soname ``libamdhip64.so.7``), so the
   extension shares torch's streams and caching allocator.
+* ``csrc/include/tp_launchers.h`` is the one place a launcher is declared; kernel files, bindings
+  and the host validation programs all include it.
+* ``build_host_program(name)`` builds one of the ``csrc/tests/*_validation.cpp`` programs of
+  ``HOST_PROGRAMS`` against the kernel files it calls, with AddressSanitizer + UBSan on the host
+  code, into ``build/asan``.
 
 The reference has no native code at all; this replaces the
 implicit cuDNN/cuBLAS/ATen kernels its hooks trigger.
@@ -68,7 +73,7 @@ FILE_FLAGS = {"wino4": ["-fno-slp-vectorize"]}
 
 
 def _needs_rebuild(src: Path, obj: Path, deps: list[Path]) -> bool:
-    """mtime check (host-sanitizer build only; the extension itself rebuilds by content hash)."""
+    """mtime check (host validation programs only; the extension itself rebuilds by content hash)."""
     if not obj.exists():
         return True
     t = obj.stat().st_mtime
@@ -197,183 +202,44 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
     return OUT
 
 
-SANITIZE_SOURCES = ("wino4", "conv_mfma", "conv_wgrad", "winograd", "batchnorm", "weight_pack")  # longest compile first
+# ---------------------------------------------------------------- host validation programs
+# csrc/tests/<name>.cpp -> the kernel files whose launchers it calls (longest compile first). Each
+# program checks, on a CPU-only machine, that the launchers reject unsupported shapes before touching
+# the GPU and that the host-side helpers are memory-clean; no kernel is launched.
+HOST_PROGRAMS = {
+    "launcher_validation": ("wino4", "conv_mfma", "conv_wgrad", "winograd", "batchnorm", "weight_pack"),
+    "dwconv_validation": ("dwconv",),
+    "dwconv_act_validation": ("dwconv_act",),
+    "dwconv_carried_validation": ("dwconv", "batchnorm"),
+    "se_validation": ("squeeze_excite",),
+    "prefix_project_validation": ("prefix_project",),
+    "conv2x2_fast_validation": ("conv_mfma", "conv2x2_fast"),
+    "elementwise_validation": ("channel_reduce", "prune_ops", "shapley", "train_ops", "data_ops"),
+}
 
 
-def build_host_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/launcher_validation.cpp`` against the kernel launchers with
-    AddressSanitizer + UBSan on the HOST code only (``-Xarch_host -fsanitize=...``; GPU
-    sanitizers are not available on this pool). The program checks, on a CPU-only machine,
-    that every launcher rejects unsupported shapes before touching the GPU and that the host
-    geometry helpers are memory-clean. Returns the executable path."""
+def build_host_program(name: str, verbose: bool = False) -> Path:
+    """Build ``csrc/tests/<name>.cpp`` against the kernel files ``HOST_PROGRAMS[name]`` with
+    AddressSanitizer + UBSan on the HOST code only (``-Xarch_host -fsanitize=...``; GPU sanitizers
+    are not available on this pool). The kernel objects in ``build/asan`` are shared between the
+    programs and rebuilt by file time. Returns the executable path."""
     out_dir = ROOT / "build" / "asan"
     out_dir.mkdir(parents=True, exist_ok=True)
     headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", "-Xarch_host", "-fsanitize=address,undefined"]
     jobs, objs = [], []
-    for name in SANITIZE_SOURCES:
-        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
+    for stem in HOST_PROGRAMS[name]:
+        src, obj = CSRC / "kernels" / f"{stem}.hip", out_dir / f"{stem}.o"
         objs.append(obj)
         if _needs_rebuild(src, obj, headers):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                         "-c", src, "-o", obj])
-    test_src, test_obj = CSRC / "tests" / "launcher_validation.cpp", out_dir / "launcher_validation.o"
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=min(4, os.cpu_count() or 4)) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "launcher_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
-    return exe
-
-
-def build_dwconv_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/dwconv_validation.cpp`` against the depthwise-conv launchers
-    (``dwconv.hip``) with AddressSanitizer + UBSan on the HOST code only, like
-    :func:`build_host_sanitizer`. Returns the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    src, obj = CSRC / "kernels" / "dwconv.hip", out_dir / "dwconv.o"
-    test_src, test_obj = CSRC / "tests" / "dwconv_validation.cpp", out_dir / "dwconv_validation.o"
-    jobs = []
-    if _needs_rebuild(src, obj, headers):
-        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                     "-c", src, "-o", obj])
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "dwconv_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
-    return exe
-
-
-def build_dwconv_act_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/dwconv_act_validation.cpp`` against the fused depthwise-conv launchers
-    (``dwconv_act.hip``) with AddressSanitizer + UBSan on the HOST code only, like
-    :func:`build_dwconv_sanitizer`. Returns the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    src, obj = CSRC / "kernels" / "dwconv_act.hip", out_dir / "dwconv_act.o"
-    test_src, test_obj = CSRC / "tests" / "dwconv_act_validation.cpp", out_dir / "dwconv_act_validation.o"
-    jobs = []
-    if _needs_rebuild(src, obj, headers):
-        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                     "-c", src, "-o", obj])
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "dwconv_act_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
-    return exe
-
-
-def build_se_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/se_validation.cpp`` against the squeeze-and-excitation launchers
-    (``squeeze_excite.hip``) with AddressSanitizer + UBSan on the HOST code only, like
-    :func:`build_dwconv_sanitizer`. Returns the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    src, obj = CSRC / "kernels" / "squeeze_excite.hip", out_dir / "squeeze_excite.o"
-    test_src, test_obj = CSRC / "tests" / "se_validation.cpp", out_dir / "se_validation.o"
-    jobs = []
-    if _needs_rebuild(src, obj, headers):
-        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                     "-c", src, "-o", obj])
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "se_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
-    return exe
-
-
-def build_prefix_project_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/prefix_project_validation.cpp`` against the prefix-scan project-conv
-    launcher (``prefix_project.hip``) with AddressSanitizer + UBSan on the HOST code only, like
-    :func:`build_dwconv_act_sanitizer`. Returns the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    src, obj = CSRC / "kernels" / "prefix_project.hip", out_dir / "prefix_project.o"
-    test_src, test_obj = CSRC / "tests" / "prefix_project_validation.cpp", out_dir / "prefix_project_validation.o"
-    jobs = []
-    if _needs_rebuild(src, obj, headers):
-        jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                     "-c", src, "-o", obj])
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "prefix_project_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, obj, "-o", exe], verbose)
-    return exe
-
-
-def build_conv2x2_fast_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/conv2x2_fast_validation.cpp`` against the nine-product 2x2-map conv
-    launchers (``conv2x2_fast.hip``, and ``conv_mfma.hip`` for the batched GEMM they call; its object
-    is the one :func:`build_host_sanitizer` makes) with AddressSanitizer + UBSan on the HOST code
-    only, like :func:`build_prefix_project_sanitizer`. Returns the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    jobs, objs = [], []
-    for name in ("conv_mfma", "conv2x2_fast"):
-        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
-        objs.append(obj)
-        if _needs_rebuild(src, obj, headers):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                         "-c", src, "-o", obj])
-    test_src, test_obj = CSRC / "tests" / "conv2x2_fast_validation.cpp", out_dir / "conv2x2_fast_validation.o"
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=3) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "conv2x2_fast_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
-    return exe
-
-
-def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/dwconv_carried_validation.cpp`` against the carried-width depthwise-conv
-    launchers (``dwconv.hip``) and the BatchNorm launchers (``batchnorm.hip``) with
-    AddressSanitizer + UBSan on the HOST code only, like :func:`build_dwconv_sanitizer` (the two
-    kernel objects are the ones that build and :func:`build_host_sanitizer` make). Returns the
-    executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    jobs, objs = [], []
-    for name in ("dwconv", "batchnorm"):
-        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
-        objs.append(obj)
-        if _needs_rebuild(src, obj, headers):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                         "-c", src, "-o", obj])
-    test_src, test_obj = CSRC / "tests" / "dwconv_carried_validation.cpp", out_dir / "dwconv_carried_validation.o"
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=3) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "dwconv_carried_validation"
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", *flags, "-c", src, "-o", obj])
+    test_src, test_obj = CSRC / "tests" / f"{name}.cpp", out_dir / f"{name}.o"
+    if _needs_rebuild(test_src, test_obj, headers + [CSRC / "tests" / "tp_expect.h"]):
+        jobs.append([HIPCC, *flags, "-c", test_src, "-o", test_obj])
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
+            list(ex.map(lambda c: _run(c, verbose), jobs))
+    exe = out_dir / name
     if jobs or not exe.exists():
         _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
     return exe
@@ -382,33 +248,3 @@ def build_dwconv_carried_sanitizer(verbose: bool = False) -> Path:
 if __name__ == "__main__":
     build(verbose=True, force="--force" in sys.argv)
     print(OUT)
-
-
-ELEMENTWISE_SOURCES = ("channel_reduce", "prune_ops", "shapley", "train_ops", "data_ops")
-
-
-def build_elementwise_sanitizer(verbose: bool = False) -> Path:
-    """Build ``csrc/tests/elementwise_validation.cpp`` against the launchers of the elementwise ops
-    (``channel_reduce.hip``, ``prune_ops.hip``, ``shapley.hip``, ``train_ops.hip``, ``data_ops.hip``)
-    with AddressSanitizer + UBSan on the HOST code only, like :func:`build_se_sanitizer`. Returns
-    the executable path."""
-    out_dir = ROOT / "build" / "asan"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "include").glob("*.h"))
-    san = ["-Xarch_host", "-fsanitize=address,undefined"]
-    jobs, objs = [], []
-    for name in ELEMENTWISE_SOURCES:
-        src, obj = CSRC / "kernels" / f"{name}.hip", out_dir / f"{name}.o"
-        objs.append(obj)
-        if _needs_rebuild(src, obj, headers):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", f"-I{CSRC / 'include'}", *san,
-                         "-c", src, "-o", obj])
-    test_src, test_obj = CSRC / "tests" / "elementwise_validation.cpp", out_dir / "elementwise_validation.o"
-    if _needs_rebuild(test_src, test_obj, headers):
-        jobs.append([HIPCC, "-O1", "-g", "-std=c++17", *san, "-c", test_src, "-o", test_obj])
-    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 4)) as ex:
-        list(ex.map(lambda c: _run(c, verbose), jobs))
-    exe = out_dir / "elementwise_validation"
-    if jobs or not exe.exists():
-        _run([HIPCC, f"--offload-arch={ARCH}", "-fsanitize=address,undefined", test_obj, *objs, "-o", exe], verbose)
-    return exe
