@@ -1,29 +1,12 @@
-// torch.ops.tpamd.* registrations for the gfx950 kernels. This is the only translation
-// unit that sees torch headers; kernels live in csrc/kernels/*.hip behind C launchers.
-// Every op validates device/dtype/layout and throws (TORCH_CHECK) instead of silently
-// falling back: on a GPU box the HIP path is the one that runs, or the call fails.
-#include <torch/library.h>
-#include <ATen/ATen.h>
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <hip/hip_runtime.h>
-
-#include "tp_launchers.h"
+// torch.ops.tpamd.* registrations for the gfx950 kernels: the TORCH_LIBRARY block and the pruning,
+// attribution, training, depthwise and squeeze-excite ops (the conv / GEMM / BN engine ops are in
+// engine_bindings.cpp). Only these two translation units see torch headers; kernels live in
+// csrc/kernels/*.hip behind C launchers. Every op validates device/dtype/layout and throws
+// (TORCH_CHECK) instead of silently falling back: on a GPU box the HIP path is the one that runs, or
+// the call fails. The checks both files share are in tp_bind.h.
+#include "tp_bind.h"
 
 namespace {
-
-inline hipStream_t cur_stream() { return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
-
-#define TP_CHECK_HIP(expr)                                                     \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    TORCH_CHECK(_e == hipSuccess, "tpamd kernel launch failed: ", hipGetErrorString(_e)); \
-  } while (0)
-
-void check_cuda_f32(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32, got ", t.scalar_type());
-}
 
 // Returns (B, C, S) and whether the tensor is channels_last. Accepts (B,C), (B,C,*) contiguous,
 // or 4D channels_last.
@@ -48,13 +31,13 @@ at::Tensor channel_reduce(const c10::optional<at::Tensor>& act, const c10::optio
                           int64_t mode) {
   const at::Tensor& ref = act.has_value() ? *act : *grad;
   TORCH_CHECK(act.has_value() || grad.has_value(), "channel_reduce needs act or grad");
-  check_cuda_f32(ref, "input");
+  need(ref, "input");
   BCS s = bcs_of(ref);
   if (act.has_value() && grad.has_value()) {
     TORCH_CHECK(act->sizes() == grad->sizes(), "act/grad shape mismatch");
     BCS s2 = bcs_of(*grad);
     TORCH_CHECK(s2.cl == s.cl, "act/grad layout mismatch");
-    check_cuda_f32(*grad, "grad");
+    need(*grad, "grad");
   }
   const bool need_a = (mode == 0 || mode == 1 || mode == 3);
   const bool need_g = (mode != 3);
@@ -78,13 +61,13 @@ at::Tensor channel_reduce(const c10::optional<at::Tensor>& act, const c10::optio
 }
 
 void column_accumulate(const at::Tensor& v, at::Tensor& acc_sum, const c10::optional<at::Tensor>& acc_sq) {
-  check_cuda_f32(v, "v");
+  need(v, "v");
   TORCH_CHECK(v.dim() == 2 && v.is_contiguous(), "v must be contiguous (B, C)");
   TORCH_CHECK(acc_sum.device() == v.device() && acc_sum.scalar_type() == at::kDouble &&
                   acc_sum.numel() == v.size(1) && acc_sum.is_contiguous(),
               "acc_sum must be a contiguous float64 (C,) tensor on v's device");
   double* sq = nullptr;
-  if (acc_sq.has_value()) {
+  if (present(acc_sq)) {
     TORCH_CHECK(acc_sq->device() == v.device() && acc_sq->scalar_type() == at::kDouble &&
                     acc_sq->numel() == v.size(1) && acc_sq->is_contiguous(),
                 "acc_sq must be a contiguous float64 (C,) tensor on v's device");
@@ -116,7 +99,7 @@ void score_fold_(at::TensorList T, at::TensorList acc, bool take_abs, int64_t af
     tp.clear(); ap.clear(); bs.clear(); cs.clear(); rs.clear();
   };
   for (size_t i = 0; i < T.size(); ++i) {
-    check_cuda_f32(T[i], "T");
+    need(T[i], "T");
     TORCH_CHECK(T[i].device() == T[0].device(), "score tensors must share a device");
     TORCH_CHECK((T[i].dim() == 2 || T[i].dim() == 3) && T[i].is_contiguous(),
                 "T must be contiguous (B, C) or (R, B, C) partial slots");
@@ -139,7 +122,7 @@ void score_fold_(at::TensorList T, at::TensorList acc, bool take_abs, int64_t af
 }
 
 void channel_fill_(at::Tensor& x, const at::Tensor& idx, double value) {
-  check_cuda_f32(x, "x");
+  need(x, "x");
   TORCH_CHECK(x.is_contiguous(), "channel_fill_ needs a contiguous NC* tensor");
   TORCH_CHECK(idx.scalar_type() == at::kLong && idx.device() == x.device() && idx.dim() == 1,
               "idx must be int64 (n,) on x's device");
@@ -152,7 +135,7 @@ void channel_fill_(at::Tensor& x, const at::Tensor& idx, double value) {
 }
 
 at::Tensor nan_channels(const at::Tensor& x_) {
-  check_cuda_f32(x_, "x");
+  need(x_, "x");
   auto x = x_.contiguous();
   BCS s = bcs_of(x);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -214,7 +197,7 @@ std::vector<at::Tensor> gather_multi(at::TensorList srcs, at::IntArrayRef axes, 
 }
 
 at::Tensor prefix_mask(const at::Tensor& z, const at::Tensor& rank, int64_t p0, int64_t K) {
-  check_cuda_f32(z, "z");
+  need(z, "z");
   TORCH_CHECK(rank.scalar_type() == at::kInt && rank.device() == z.device() && rank.dim() == 1 && rank.is_contiguous(),
               "rank must be a contiguous int32 (C,) tensor on z's device");
   BCS s = bcs_of(z);
@@ -236,10 +219,10 @@ at::Tensor prefix_mask(const at::Tensor& z, const at::Tensor& rank, int64_t p0, 
 // of a 1x1 project conv whose input copies differ by one filled channel each (csrc/kernels/prefix_project.hip)
 at::Tensor prefix_project(const at::Tensor& base, const at::Tensor& a, const at::Tensor& fill, const at::Tensor& wt,
                           const at::Tensor& perm, int64_t p0, int64_t cnt) {
-  check_cuda_f32(base, "base");
-  check_cuda_f32(a, "a");
-  check_cuda_f32(fill, "fill");
-  check_cuda_f32(wt, "wt");
+  need(base, "base");
+  need(a, "a");
+  need(fill, "fill");
+  need(wt, "wt");
   TORCH_CHECK(base.dim() == 2 && base.is_contiguous() && base.numel() > 0, "base must be a non-empty contiguous (N, Co)");
   const int64_t N = base.size(0), Co = base.size(1);
   TORCH_CHECK(a.dim() == 2 && a.is_contiguous() && a.size(0) == N && a.size(1) > 0, "a must be a contiguous (N, C)");
@@ -267,7 +250,7 @@ at::Tensor prefix_project(const at::Tensor& base, const at::Tensor& a, const at:
 
 void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv, int64_t row0, int64_t k0,
                      double scale) {
-  check_cuda_f32(L, "losses");
+  need(L, "losses");
   TORCH_CHECK(L.dim() == 2 && L.is_contiguous(), "losses must be contiguous (K+1, B)");
   TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous() && perm.device() == L.device(),
               "perm must be int32 on the losses' device");
@@ -285,7 +268,7 @@ void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv
 }
 
 void shapley_column(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv_col, int64_t k0, double scale) {
-  check_cuda_f32(L, "losses");
+  need(L, "losses");
   TORCH_CHECK(L.dim() == 2 && L.is_contiguous(), "losses must be contiguous (K+1, B)");
   TORCH_CHECK(perm.scalar_type() == at::kInt && perm.is_contiguous() && perm.device() == L.device(),
               "perm must be int32 on the losses' device");
@@ -303,7 +286,7 @@ void shapley_column(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv_
 
 std::tuple<at::Tensor, at::Tensor> cross_entropy(const at::Tensor& logits_, const at::Tensor& target_,
                                                  double gscale, bool want_grad) {
-  check_cuda_f32(logits_, "logits");
+  need(logits_, "logits");
   TORCH_CHECK(logits_.dim() == 2, "logits must be (B, classes)");
   auto logits = logits_.contiguous();
   TORCH_CHECK(target_.device() == logits_.device(), "target must be on the logits' device");
@@ -331,13 +314,13 @@ at::Tensor augment_u8(const at::Tensor& src, const at::Tensor& idx, const c10::o
               "idx must be a contiguous int64 GPU vector");
   const int64_t B = idx.size(0), C = src.size(1), H = src.size(2), W = src.size(3);
   const int* ap = nullptr;
-  if (aug.has_value() && aug->defined()) {
+  if (present(aug)) {
     TORCH_CHECK(aug->is_cuda() && aug->scalar_type() == at::kInt && aug->is_contiguous() && aug->numel() == 3 * B,
                 "aug must be a contiguous int32 (B, 3) GPU tensor");
     ap = aug->data_ptr<int>();
   }
-  check_cuda_f32(mean, "mean");
-  check_cuda_f32(inv_std, "inv_std");
+  need(mean, "mean");
+  need(inv_std, "inv_std");
   TORCH_CHECK(mean.numel() == C && inv_std.numel() == C && mean.is_contiguous() && inv_std.is_contiguous(),
               "mean / inv_std must have C elements");
   TORCH_CHECK(pad >= 0, "pad must be >= 0");
@@ -354,7 +337,7 @@ at::Tensor augment_u8(const at::Tensor& src, const at::Tensor& idx, const c10::o
 
 // Inverted dropout with a counter-based Philox mask (forward and, with the same seed, backward).
 at::Tensor dropout(const at::Tensor& x_, int64_t seed, double p) {
-  check_cuda_f32(x_, "x");
+  need(x_, "x");
   auto x = x_.contiguous();
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -371,7 +354,7 @@ at::Tensor dropout(const at::Tensor& x_, int64_t seed, double p) {
 // Training max-pool on NHWC (B, H, W, C), C % 4 == 0: (y, window-local argmax bytes); the
 // backward gathers (deterministic). avgpool_bwd: global average pool gradient (B, C) -> (B, H, W, C).
 std::tuple<at::Tensor, at::Tensor> maxpool_train_fwd(const at::Tensor& x, int64_t k, int64_t s, int64_t pad) {
-  check_cuda_f32(x, "x");
+  need(x, "x");
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.size(3) % 4 == 0, "x must be contiguous NHWC with C % 4 == 0");
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
@@ -386,16 +369,16 @@ std::tuple<at::Tensor, at::Tensor> maxpool_train_fwd(const at::Tensor& x, int64_
 
 at::Tensor maxpool_train_bwd(const at::Tensor& g_, const at::Tensor& am, int64_t H, int64_t W, int64_t k, int64_t s,
                              int64_t pad) {
-  check_cuda_f32(g_, "g");
+  need(g_, "g");
   auto g = g_.contiguous();
-  TORCH_CHECK(g.dim() == 4 && am.sizes() == g.sizes() && am.scalar_type() == at::kByte && am.is_contiguous() &&
-                  am.device() == g.device(), "am must be the forward's (B, Ho, Wo, C) uint8 argmax");
+  TORCH_CHECK(g.dim() == 4, "g must be (B, Ho, Wo, C)");
+  const uint8_t* amp = argmax_ptr(am, "am", g);  // the forward's window-local argmax
   const int64_t B = g.size(0), C = g.size(3);
   TORCH_CHECK(g.size(1) == (H + 2 * pad - k) / s + 1 && g.size(2) == (W + 2 * pad - k) / s + 1, "g shape mismatch");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   auto dx = at::empty({B, H, W, C}, g.options());
-  TP_CHECK_HIP(tp_maxpool_bwd(g.data_ptr<float>(), am.data_ptr<uint8_t>(), dx.data_ptr<float>(), (int)B, (int)H,
-                              (int)W, (int)C, (int)k, (int)s, (int)pad, cur_stream()));
+  TP_CHECK_HIP(tp_maxpool_bwd(g.data_ptr<float>(), amp, dx.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)k,
+                              (int)s, (int)pad, cur_stream()));
   return dx;
 }
 
@@ -409,7 +392,7 @@ void check_dw_geometry(int64_t H, int64_t W, int64_t k, int64_t s, int64_t pad) 
 }
 
 void check_dw_weight(const at::Tensor& w, int64_t C, const at::Tensor& like) {
-  check_cuda_f32(w, "w");
+  need(w, "w");
   TORCH_CHECK(w.dim() == 4 && w.size(0) >= 1 && w.size(0) <= C && w.size(1) == 1 && w.size(2) == w.size(3) &&
                   w.is_contiguous() && w.device() == like.device(),
               "w must be a contiguous (Cw, 1, k, k) depthwise weight with Cw <= the activation's channels");
@@ -418,7 +401,7 @@ void check_dw_weight(const at::Tensor& w, int64_t C, const at::Tensor& like) {
 
 at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, int64_t s,
                       int64_t pad) {
-  check_cuda_f32(x, "x");
+  need(x, "x");
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "x must be a non-empty contiguous NHWC tensor");
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   check_dw_weight(w, C, x);
@@ -426,10 +409,10 @@ at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
   check_dw_geometry(H, W, k, s, pad);
   TORCH_CHECK(x.numel() < (int64_t(1) << 29), "x exceeds the kernels' 2 GiB operand range");
   const float* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    check_cuda_f32(*bias, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == w.size(0) && bias->is_contiguous() &&
-                    bias->device() == x.device(), "bias must be a contiguous (Cw,) tensor");
+  if (present(bias)) {
+    need(*bias, "bias", kAnyLayout, &x);
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == w.size(0) && bias->is_contiguous(),
+                "bias must be a contiguous (Cw,) tensor");
     bp = bias->data_ptr<float>();
   }
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -440,7 +423,7 @@ at::Tensor dwconv_fwd(const at::Tensor& x, const at::Tensor& w, const c10::optio
 }
 
 at::Tensor dwconv_dgrad(const at::Tensor& g_, const at::Tensor& w, int64_t H, int64_t W, int64_t s, int64_t pad) {
-  check_cuda_f32(g_, "g");
+  need(g_, "g");
   auto g = g_.contiguous();
   TORCH_CHECK(g.dim() == 4 && g.numel() > 0 && H > 0 && W > 0, "g must be a non-empty (B, Ho, Wo, C) tensor");
   const int64_t B = g.size(0), C = g.size(3);
@@ -462,9 +445,9 @@ at::Tensor dwconv_dgrad(const at::Tensor& g_, const at::Tensor& w, int64_t H, in
 // carried width, a multiple of 4 then): the gradients cover the Cw channels of the parameter.
 c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x, int64_t k, int64_t s, int64_t pad,
                                        at::Tensor& dw, bool want_bias) {
-  check_cuda_f32(g_, "g");
-  check_cuda_f32(x, "x");
-  check_cuda_f32(dw, "dw");
+  need(g_, "g");
+  need(x, "x");
+  need(dw, "dw");
   auto g = g_.contiguous();
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && g.dim() == 4 && g.numel() > 0 && x.device() == g.device(),
               "g / x must be non-empty contiguous NHWC tensors on one device");
@@ -494,15 +477,15 @@ c10::optional<at::Tensor> dwconv_wgrad(const at::Tensor& g_, const at::Tensor& x
 
 void check_dwa_params(const at::Tensor& w, const at::Tensor& scale, const at::Tensor* shift, int64_t C,
                       const at::Tensor& like) {
-  check_cuda_f32(w, "w");
-  check_cuda_f32(scale, "scale");
+  need(w, "w");
+  need(scale, "scale");
   TORCH_CHECK(C % 4 == 0, "dwconv_act needs a channel count that is a multiple of 4 (pad the channels), got ", C);
   TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == w.size(3) && w.is_contiguous() &&
                   w.device() == like.device(), "w must be a contiguous (C, 1, k, k) depthwise weight");
   TORCH_CHECK(scale.dim() == 1 && scale.size(0) == C && scale.is_contiguous() && scale.device() == like.device(),
               "scale must be a contiguous (C,) tensor");
   if (shift != nullptr) {
-    check_cuda_f32(*shift, "shift");
+    need(*shift, "shift");
     TORCH_CHECK(shift->dim() == 1 && shift->size(0) == C && shift->is_contiguous() && shift->device() == like.device(),
                 "shift must be a contiguous (C,) tensor");
   }
@@ -517,7 +500,7 @@ void check_dwa_acts(int64_t in_act, int64_t out_act) {
 at::Tensor dwconv_act_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
                           int64_t s, int64_t pad, int64_t in_act, int64_t out_act,
                           const c10::optional<at::Tensor>& apoz) {
-  check_cuda_f32(x, "x");
+  need(x, "x");
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "x must be a non-empty contiguous NHWC tensor");
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   check_dwa_params(w, scale, &shift, C, x);
@@ -526,10 +509,9 @@ at::Tensor dwconv_act_fwd(const at::Tensor& x, const at::Tensor& w, const at::Te
   check_dw_geometry(H, W, k, s, pad);
   TORCH_CHECK(x.numel() < (int64_t(1) << 29), "x exceeds the kernels' 2 GiB operand range");
   float* ap = nullptr;
-  if (apoz.has_value() && apoz->defined()) {
-    check_cuda_f32(*apoz, "apoz");
-    TORCH_CHECK(apoz->dim() == 2 && apoz->size(0) == B && apoz->size(1) == C && apoz->is_contiguous() &&
-                    apoz->device() == x.device(), "apoz must be a contiguous (B, C) tensor");
+  if (present(apoz)) {  // (stricter than count_ptr: the (B, C) shape itself)
+    need(*apoz, "apoz", 2, &x);
+    TORCH_CHECK(apoz->size(0) == B && apoz->size(1) == C, "apoz must be a contiguous (B, C) tensor");
     ap = apoz->data_ptr<float>();
   }
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -551,9 +533,9 @@ int64_t dwconv_act_tay_slots(int64_t H, int64_t W, int64_t C) {
 at::Tensor dwconv_act_dgrad(const at::Tensor& g, const at::Tensor& y, const at::Tensor& w, const at::Tensor& scale,
                             const at::Tensor& z, int64_t H, int64_t W, int64_t s, int64_t pad, int64_t in_act,
                             int64_t out_act, const c10::optional<at::Tensor>& tay, int64_t tay_mode) {
-  check_cuda_f32(g, "g");
-  check_cuda_f32(y, "y");
-  check_cuda_f32(z, "z");
+  need(g, "g");
+  need(y, "y");
+  need(z, "z");
   TORCH_CHECK(z.dim() == 4 && z.is_contiguous() && z.numel() > 0 && z.size(1) == H && z.size(2) == W,
               "z must be a non-empty contiguous (B, H, W, C) tensor");
   const int64_t B = z.size(0), C = z.size(3);
@@ -568,8 +550,8 @@ at::Tensor dwconv_act_dgrad(const at::Tensor& g, const at::Tensor& y, const at::
   TORCH_CHECK(z.numel() < (int64_t(1) << 29), "z exceeds the kernels' 2 GiB operand range");
   float* tp = nullptr;
   int R = 0;
-  if (tay.has_value() && tay->defined()) {
-    check_cuda_f32(*tay, "tay");
+  if (present(tay)) {
+    need(*tay, "tay");
     TORCH_CHECK(tay_mode == 0 || tay_mode == 1, "tay_mode is 0 (Taylor) or 1 (Sensitivity)");
     R = tp_dwconv_act_tay_slots((int)H, (int)W, (int)C);
     TORCH_CHECK(tay->dim() == 3 && tay->size(0) == R && tay->size(1) == B && tay->size(2) == C &&
@@ -588,7 +570,7 @@ at::Tensor dwconv_act_dgrad(const at::Tensor& g, const at::Tensor& y, const at::
 }
 
 at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
-  check_cuda_f32(g_, "g");
+  need(g_, "g");
   auto g = g_.contiguous();
   TORCH_CHECK(g.dim() == 2 && g.size(1) % 4 == 0 && H > 0 && W > 0, "g must be (B, C) with C % 4 == 0");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
@@ -600,29 +582,29 @@ at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
 
 // ---- squeeze-and-excitation gates (squeeze_excite.hip): x / g (B, H, W, C) NHWC, rows (B, C) / (B, Cs)
 void check_se_act(const at::Tensor& x, const char* name) {
-  check_cuda_f32(x, name);
+  need(x, name);
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, name, " must be a non-empty contiguous NHWC tensor");
   TORCH_CHECK(x.numel() < (int64_t(1) << 29), name, " exceeds the kernels' 2 GiB operand range");
   TORCH_CHECK(x.size(0) <= 65535, name, ": more than 65535 images per call");
 }
 
 void check_se_rows(const at::Tensor& t, int64_t B, int64_t n, const at::Tensor& like, const char* name) {
-  check_cuda_f32(t, name);
+  need(t, name);
   TORCH_CHECK(t.dim() == 2 && t.size(0) == B && t.size(1) == n && t.is_contiguous() && t.device() == like.device(),
               name, " must be a contiguous (", B, ", ", n, ") tensor on the same device");
 }
 
 // fc weights in the parameter's layout: (out, in) or (out, in, 1, 1), contiguous
 void check_se_weight(const at::Tensor& w, int64_t n_out, int64_t n_in, const at::Tensor& like, const char* name) {
-  check_cuda_f32(w, name);
+  need(w, name);
   TORCH_CHECK((w.dim() == 2 || (w.dim() == 4 && w.size(2) == 1 && w.size(3) == 1)) && w.size(0) == n_out &&
                   w.size(1) == n_in && w.is_contiguous() && w.device() == like.device(),
               name, " must be a contiguous (", n_out, ", ", n_in, "[, 1, 1]) weight on the same device");
 }
 
 const float* se_bias(const c10::optional<at::Tensor>& b, int64_t n, const at::Tensor& like, const char* name) {
-  if (!b.has_value() || !b->defined()) return nullptr;
-  check_cuda_f32(*b, name);
+  if (!present(b)) return nullptr;
+  need(*b, name);
   TORCH_CHECK(b->dim() == 1 && b->size(0) == n && b->is_contiguous() && b->device() == like.device(), name,
               " must be a contiguous (", n, ",) tensor on the same device");
   return b->data_ptr<float>();
@@ -666,7 +648,7 @@ at::Tensor se_bwd_reduce(const at::Tensor& g, const at::Tensor& x) {
 std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Tensor& w1,
                                                const c10::optional<at::Tensor>& b1, const at::Tensor& w2,
                                                const c10::optional<at::Tensor>& b2, int64_t gate) {
-  check_cuda_f32(p, "p");
+  need(p, "p");
   TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && p.numel() > 0, "p must be a non-empty contiguous (B, C) tensor");
   TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
   const int64_t B = p.size(0), C = p.size(1);
@@ -690,7 +672,7 @@ std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Te
 std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_bwd(const at::Tensor& ds, const at::Tensor& s,
                                                            const at::Tensor& h, const at::Tensor& w1,
                                                            const at::Tensor& w2, int64_t gate) {
-  check_cuda_f32(ds, "ds");
+  need(ds, "ds");
   TORCH_CHECK(ds.dim() == 2 && ds.is_contiguous() && ds.numel() > 0, "ds must be a non-empty contiguous (B, C) tensor");
   TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
   TORCH_CHECK(h.dim() == 2, "h must be (B, Cs)");
@@ -737,8 +719,8 @@ at::Tensor se_bwd_dx(const at::Tensor& g, const at::Tensor& s, const at::Tensor&
 // dW[r, k] = sum_b a[b, r] * m[b, k] written into ``dw`` ((R, K) or (R, K, 1, 1)) with that tensor's own
 // strides (the parameter's: DDP bucket views); returns db[r] = sum_b a[b, r] when asked for
 c10::optional<at::Tensor> se_wgrad(const at::Tensor& a, const at::Tensor& m, at::Tensor& dw, bool want_bias) {
-  check_cuda_f32(a, "a");
-  check_cuda_f32(dw, "dw");
+  need(a, "a");
+  need(dw, "dw");
   TORCH_CHECK(a.dim() == 2 && a.is_contiguous() && a.numel() > 0 && m.dim() == 2, "a / m must be (B, R) / (B, K) rows");
   const int64_t B = a.size(0), R = a.size(1), K = m.size(1);
   check_se_rows(m, B, K, a, "m");

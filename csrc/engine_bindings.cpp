@@ -1,86 +1,43 @@
-// torch.ops.tpamd.* registrations for the fused conv / GEMM engine kernels (conv_mfma.hip).
-#include <torch/library.h>
-#include <ATen/ATen.h>
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <hip/hip_runtime.h>
-
-#include "tp_launchers.h"
+// torch.ops.tpamd.* registrations of the engine kernels: the implicit-GEMM, GEN and first-layer convs and the
+// Shapley prefix GEMM (conv_mfma.hip), the 2x2-map conv (conv2x2_fast.hip), Winograd F(2x2) / F(4x4)
+// (winograd.hip, wino4.hip), the weight gradients (conv_wgrad.hip, wino_wgrad.hip), weight packing
+// (weight_pack.hip), training BatchNorm (batchnorm.hip) and the NHWC pools (prune_ops.hip). The operand
+// checks shared by these ops are in tp_bind.h.
+#include "tp_bind.h"
 
 namespace {
 
-inline hipStream_t cur_stream() { return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
-
-#define TP_CHECK_HIP(expr)                                                                  \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    TORCH_CHECK(_e == hipSuccess, "tpamd conv launch failed: ", hipGetErrorString(_e));     \
-  } while (0)
-
-void need(const at::Tensor& t, const char* name, int64_t dim) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat, name, " must be a float32 GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(dim < 0 || t.dim() == dim, name, " must have ", dim, " dims, got ", t.dim());
-}
-
-const float* opt_ptr(const c10::optional<at::Tensor>& t, int64_t n, const char* name) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  need(*t, name, 1);
-  TORCH_CHECK(t->numel() == n, name, " must have ", n, " elements");
-  // the epilogues read per-channel vectors as float4
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr<float>()) % 16 == 0, name, " must be 16-byte aligned");
-  return t->data_ptr<float>();
-}
-
 enum { EPI_FWD = 0, EPI_FWD_POOL = 1, EPI_BWD = 2 };
 
-int64_t splits_ws(int64_t splits, int64_t K) {
-  const int64_t kt = K / 32;
-  splits = std::max<int64_t>(1, std::min<int64_t>(splits, kt));
-  const int64_t per = (kt + splits - 1) / splits;
-  return (kt + per - 1) / per;
+void check_igemm_cfg(int64_t cfg, int64_t ks) {
+  TORCH_CHECK((cfg >= 0 && cfg <= 6) || (ks == 3 && (cfg == 256 || cfg == 258 || cfg == 259)),
+              "bad tile config (bf16 operands: 256 + {0, 2, 3}, 3x3 only)");
 }
 
 // Forward conv / linear: x (B,H,W,Cin) NHWC, w (Cout, K) with K = ks*ks*Cin.
 // Returns out (B,H,W,Cout) or pooled (B,H/2,W/2,Cout) + argmax bytes.
-std::tuple<at::Tensor, at::Tensor> conv_fwd(const at::Tensor& x, const at::Tensor& w,
-                                            const c10::optional<at::Tensor>& scale,
-                                            const c10::optional<at::Tensor>& shift, bool relu, bool pool, int64_t ks,
-                                            int64_t cfg, int64_t splits, const c10::optional<at::Tensor>& apoz,
-                                            double slope) {
+std::tuple<at::Tensor, at::Tensor> conv_fwd(const at::Tensor& x, const at::Tensor& w, const OptTensor& scale,
+                                            const OptTensor& shift, bool relu, bool pool, int64_t ks, int64_t cfg,
+                                            int64_t splits, const OptTensor& apoz, double slope) {
   need(x, "x", 4);
-  need(w, "w", 2);
+  need(w, "w", 2, &x);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = w.size(0);
   TORCH_CHECK(ks == 1 || ks == 3, "ks must be 1 or 3");
   TORCH_CHECK(w.size(1) == ks * ks * Cin, "weight K mismatch: ", w.size(1), " vs ", ks * ks * Cin);
   TORCH_CHECK(Cin % 32 == 0, "Cin must be a multiple of 32");
   TORCH_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), "pooling needs even H, W");
-  TORCH_CHECK((cfg >= 0 && cfg <= 6) || (ks == 3 && (cfg == 256 || cfg == 258 || cfg == 259)),
-              "bad tile config (bf16 operands: 256 + {0, 2, 3}, 3x3 only)");
+  check_igemm_cfg(cfg, ks);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sc = opt_ptr(scale, Cout, "scale");
-  const float* sh = opt_ptr(shift, Cout, "shift");
-  at::Tensor out, am;
-  if (pool) {
-    out = at::empty({B, H / 2, W / 2, Cout}, x.options());
-    am = at::empty({B, H / 2, W / 2, Cout}, x.options().dtype(at::kByte));
-  } else {
-    out = at::empty({B, H, W, Cout}, x.options());
-  }
-  const int64_t sp = splits_ws(splits, ks * ks * Cin);
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * Cout}, x.options());
-  float* ap = nullptr;  // (B, Cout) counts of positive (pre-pool) outputs, accumulated
-  if (apoz.has_value() && apoz->defined()) {
-    TORCH_CHECK(apoz->is_cuda() && apoz->scalar_type() == at::kFloat && apoz->is_contiguous() &&
-                    apoz->numel() == B * Cout, "apoz must be a contiguous float32 (B, Cout) tensor");
-    ap = apoz->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(scale, Cout, "scale", x);
+  const float* sh = opt_ptr(shift, Cout, "shift", x);
+  auto [out, am] = conv_out(x, B, H, W, Cout, pool);
+  const int64_t sp = norm_splits(splits, ks * ks * Cin / 32);
+  at::Tensor ws = splitk_ws(sp, B * H * W * Cout, x);
+  float* ap = count_ptr(apoz, B, Cout, x);  // counts of positive (pre-pool) outputs
   TP_CHECK_HIP(tp_conv_igemm(x.data_ptr<float>(), nullptr, w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin,
                              (int)Cout, (int)ks, pool ? 1 : 0, 0, pool ? EPI_FWD_POOL : EPI_FWD, (int)cfg, (int)sp, sc,
                              sh, relu ? 1 : 0, out.data_ptr<float>(), pool ? am.data_ptr<uint8_t>() : nullptr, nullptr,
-                             nullptr, (int)(H * W), 0, sp > 1 ? ws.data_ptr<float>() : nullptr, 0, ap, (float)slope,
-                             cur_stream()));
+                             nullptr, (int)(H * W), 0, ptr_or_null(ws), 0, ap, (float)slope, cur_stream()));
   return {out, am};
 }
 
@@ -90,76 +47,51 @@ std::tuple<at::Tensor, at::Tensor> conv_fwd(const at::Tensor& x, const at::Tenso
 // wt: flipped/transposed weight (Cin, ks*ks*Cout). act: activation at the conv input (B,H,W,Cin).
 // taylor (B,Cin) fp32 accumulated atomically with sum_hw -(dL/dact * act) (nullable).
 // Returns dL/d(pre-activation) * bn_scale masked by act>0 (B,H,W,Cin), or an empty tensor.
-at::Tensor conv_dgrad(const at::Tensor& g, const c10::optional<at::Tensor>& g_argmax, const at::Tensor& wt,
-                      const at::Tensor& act, const c10::optional<at::Tensor>& bn_scale,
-                      const c10::optional<at::Tensor>& taylor, bool want_out, int64_t ks, int64_t cfg,
+at::Tensor conv_dgrad(const at::Tensor& g, const OptTensor& g_argmax, const at::Tensor& wt, const at::Tensor& act,
+                      const OptTensor& bn_scale, const OptTensor& taylor, bool want_out, int64_t ks, int64_t cfg,
                       int64_t splits, int64_t tay_group, int64_t tay_mode, double slope) {
   need(g, "g", 4);
-  need(wt, "wt", 2);
-  need(act, "act", 4);
-  const bool unpool = g_argmax.has_value() && g_argmax->defined();
+  need(wt, "wt", 2, &g);
+  need(act, "act", 4, &g);
   const int64_t B = act.size(0), H = act.size(1), W = act.size(2), Cin = act.size(3);
   const int64_t Cout = g.size(3);
-  if (unpool) {
-    TORCH_CHECK(g.size(1) * 2 == H && g.size(2) * 2 == W, "pooled grad shape mismatch");
-    TORCH_CHECK(g_argmax->scalar_type() == at::kByte && g_argmax->sizes() == g.sizes() && g_argmax->is_contiguous(),
-                "g_argmax must be uint8 with g's shape");
-  } else {
-    TORCH_CHECK(g.size(1) == H && g.size(2) == W, "grad shape mismatch");
-  }
-  TORCH_CHECK(g.size(0) == B, "batch mismatch");
+  const uint8_t* am = pooled_grad(g, g_argmax, B, H, W);
   TORCH_CHECK(wt.size(0) == Cin && wt.size(1) == ks * ks * Cout, "wt must be (Cin, ks*ks*Cout)");
   TORCH_CHECK(Cout % 32 == 0, "Cout must be a multiple of 32 for dgrad");
   TORCH_CHECK(tay_group >= 0 && (tay_group == 0 || Cin % tay_group == 0), "tay_group must divide Cin");
-  TORCH_CHECK((cfg >= 0 && cfg <= 6) || (ks == 3 && (cfg == 256 || cfg == 258 || cfg == 259)),
-              "bad tile config (bf16 operands: 256 + {0, 2, 3}, 3x3 only)");
+  check_igemm_cfg(cfg, ks);
+  const int tm = tay_mode_arg(tay_mode, 2);  // the launcher passes it on unchecked
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale");
-  float* tay = nullptr;
-  if (taylor.has_value() && taylor->defined()) {
-    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
-                    taylor->numel() > 0 && taylor->numel() % (B * Cin) == 0,
-                "taylor must be a contiguous float32 (B, Cin) or (R, B, Cin) GPU tensor (slot 0 is written)");
-    tay = taylor->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale", g);
+  float* tay = taylor_ptr(taylor, 1, false, B, Cin, g);  // (B, Cin) or (R, B, Cin): slot 0 is written
   at::Tensor out;
   if (want_out) out = at::empty({B, H, W, Cin}, g.options());
-  const int64_t sp = splits_ws(splits, ks * ks * Cout);
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * Cin}, g.options());
-  TP_CHECK_HIP(tp_conv_igemm(g.data_ptr<float>(), unpool ? g_argmax->data_ptr<uint8_t>() : nullptr,
-                             wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cout, (int)Cin, (int)ks, 0,
-                             unpool ? 1 : 0, EPI_BWD, (int)cfg, (int)sp, sc, nullptr, 0,
-                             want_out ? out.data_ptr<float>() : nullptr, nullptr, act.data_ptr<float>(), tay,
-                             (int)(H * W), (int)tay_group, sp > 1 ? ws.data_ptr<float>() : nullptr, (int)tay_mode,
-                             nullptr, (float)slope, cur_stream()));
+  const int64_t sp = norm_splits(splits, ks * ks * Cout / 32);
+  at::Tensor ws = splitk_ws(sp, B * H * W * Cin, g);
+  TP_CHECK_HIP(tp_conv_igemm(g.data_ptr<float>(), am, wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cout,
+                             (int)Cin, (int)ks, 0, am ? 1 : 0, EPI_BWD, (int)cfg, (int)sp, sc, nullptr, 0,
+                             ptr_or_null(out), nullptr, act.data_ptr<float>(), tay, (int)(H * W), (int)tay_group,
+                             ptr_or_null(ws), tm, nullptr, (float)slope, cur_stream()));
   return out;
 }
 
 // 3x3 / pad-1 conv on 2x2 maps as 9 channel products (conv2x2_fast.hip). x (B,2,2,C); u9 (9,K,C) =
 // G w G^T. Returns out (B,2,2,K), or pooled (B,1,1,K) + argmax bytes.
-std::tuple<at::Tensor, at::Tensor> conv2x2_fast_fwd(const at::Tensor& x, const at::Tensor& u9,
-                                                    const c10::optional<at::Tensor>& scale,
-                                                    const c10::optional<at::Tensor>& shift, bool relu, bool pool,
-                                                    int64_t cfg, int64_t splits) {
+std::tuple<at::Tensor, at::Tensor> conv2x2_fast_fwd(const at::Tensor& x, const at::Tensor& u9, const OptTensor& scale,
+                                                    const OptTensor& shift, bool relu, bool pool, int64_t cfg,
+                                                    int64_t splits) {
   need(x, "x", 4);
-  need(u9, "u9", 3);
+  need(u9, "u9", 3, &x);
   const int64_t B = x.size(0), C = x.size(3), K = u9.size(1);
   TORCH_CHECK(x.size(1) == 2 && x.size(2) == 2, "x must be (B, 2, 2, C)");
   TORCH_CHECK(u9.size(0) == 9 && u9.size(2) == C, "u9 must be (9, K, C)");
   TORCH_CHECK(B > 0 && C % 32 == 0 && K % 4 == 0, "C must be a multiple of 32 and K of 4");
   TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sc = opt_ptr(scale, K, "scale");
-  const float* sh = opt_ptr(shift, K, "shift");
+  const float* sc = opt_ptr(scale, K, "scale", x);
+  const float* sh = opt_ptr(shift, K, "shift", x);
   const int64_t sp = tp_conv_norm_splits((int)std::max<int64_t>(1, std::min<int64_t>(splits, 1 << 16)), (int)C);
-  at::Tensor out, am;
-  if (pool) {
-    out = at::empty({B, 1, 1, K}, x.options());
-    am = at::empty({B, 1, 1, K}, x.options().dtype(at::kByte));
-  } else {
-    out = at::empty({B, 2, 2, K}, x.options());
-  }
+  auto [out, am] = conv_out(x, B, 2, 2, K, pool);
   // workspaces from the caching allocator (capturable in a HIP graph, like the split-K slabs)
   at::Tensor V = at::empty({9, B, C}, x.options()), slabs = at::empty({9 * sp, B, K}, x.options());
   TP_CHECK_HIP(tp_conv2x2_fast_fwd(x.data_ptr<float>(), u9.data_ptr<float>(), (int)B, (int)C, (int)K, (int)cfg,
@@ -171,46 +103,30 @@ std::tuple<at::Tensor, at::Tensor> conv2x2_fast_fwd(const at::Tensor& x, const a
 
 // Its data gradient with the conv_dgrad epilogue contract (tay_group = Cin: taylor is (4, B, Cin), one
 // slot per pixel, accumulated). g (B,2,2,Cg), or the pooled (B,1,1,Cg) with g_argmax; u9t (9,Cin,Cg).
-at::Tensor conv2x2_fast_dgrad(const at::Tensor& g, const c10::optional<at::Tensor>& g_argmax, const at::Tensor& u9t,
-                              const at::Tensor& act, const c10::optional<at::Tensor>& bn_scale,
-                              const c10::optional<at::Tensor>& taylor, bool want_out, int64_t cfg, int64_t splits,
-                              int64_t tay_mode) {
+at::Tensor conv2x2_fast_dgrad(const at::Tensor& g, const OptTensor& g_argmax, const at::Tensor& u9t,
+                              const at::Tensor& act, const OptTensor& bn_scale, const OptTensor& taylor, bool want_out,
+                              int64_t cfg, int64_t splits, int64_t tay_mode) {
   need(g, "g", 4);
-  need(u9t, "u9t", 3);
-  need(act, "act", 4);
-  const bool unpool = g_argmax.has_value() && g_argmax->defined();
+  need(u9t, "u9t", 3, &g);
+  need(act, "act", 4, &g);
   const int64_t B = act.size(0), Cin = act.size(3), Cg = g.size(3);
-  TORCH_CHECK(act.size(1) == 2 && act.size(2) == 2, "act must be (B, 2, 2, Cin)");
-  if (unpool) {
-    TORCH_CHECK(g.size(1) == 1 && g.size(2) == 1, "pooled grad shape mismatch");
-    TORCH_CHECK(g_argmax->scalar_type() == at::kByte && g_argmax->sizes() == g.sizes() && g_argmax->is_contiguous() &&
-                    g_argmax->is_cuda(), "g_argmax must be uint8 with g's shape");
-  } else {
-    TORCH_CHECK(g.size(1) == 2 && g.size(2) == 2, "grad shape mismatch");
-  }
-  TORCH_CHECK(g.size(0) == B && B > 0, "batch mismatch");
+  TORCH_CHECK(act.size(1) == 2 && act.size(2) == 2 && B > 0, "act must be a non-empty (B, 2, 2, Cin)");
+  const uint8_t* am = pooled_grad(g, g_argmax, B, 2, 2);
   TORCH_CHECK(u9t.size(0) == 9 && u9t.size(1) == Cin && u9t.size(2) == Cg, "u9t must be (9, Cin, Cg)");
   TORCH_CHECK(Cg % 32 == 0 && Cin % 4 == 0, "Cg must be a multiple of 32 and Cin of 4");
   TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
-  TORCH_CHECK(tay_mode >= 0 && tay_mode <= 2, "bad tay_mode");
+  const int tm = tay_mode_arg(tay_mode, 2);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale");
-  float* tay = nullptr;
-  if (taylor.has_value() && taylor->defined()) {
-    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
-                    taylor->numel() == 4 * B * Cin, "taylor must be a contiguous float32 (4, B, Cin) GPU tensor");
-    tay = taylor->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale", g);
+  float* tay = taylor_ptr(taylor, 4, true, B, Cin, g);  // one slot per pixel
   TORCH_CHECK(want_out || tay, "nothing to compute: no output and no taylor slab");
   at::Tensor out;
   if (want_out) out = at::empty({B, 2, 2, Cin}, g.options());
   const int64_t sp = tp_conv_norm_splits((int)std::max<int64_t>(1, std::min<int64_t>(splits, 1 << 16)), (int)Cg);
   at::Tensor V = at::empty({9, B, Cg}, g.options()), slabs = at::empty({9 * sp, B, Cin}, g.options());
-  TP_CHECK_HIP(tp_conv2x2_fast_dgrad(g.data_ptr<float>(), unpool ? g_argmax->data_ptr<uint8_t>() : nullptr,
-                                     u9t.data_ptr<float>(), (int)B, (int)Cg, (int)Cin, (int)cfg, (int)sp,
-                                     act.data_ptr<float>(), sc, tay, (int)tay_mode,
-                                     want_out ? out.data_ptr<float>() : nullptr, V.data_ptr<float>(),
-                                     slabs.data_ptr<float>(), cur_stream()));
+  TP_CHECK_HIP(tp_conv2x2_fast_dgrad(g.data_ptr<float>(), am, u9t.data_ptr<float>(), (int)B, (int)Cg, (int)Cin,
+                                     (int)cfg, (int)sp, act.data_ptr<float>(), sc, tay, tm, ptr_or_null(out),
+                                     V.data_ptr<float>(), slabs.data_ptr<float>(), cur_stream()));
   return out;
 }
 
@@ -218,33 +134,33 @@ at::Tensor conv2x2_fast_dgrad(const at::Tensor& g, const c10::optional<at::Tenso
 // ``wt``: optional tap-major copy of w, [Cin][3][3][Cout], packed once by the caller (the
 // wave-uniform kernel's operand layout); built here per call when absent.
 at::Tensor conv_first(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
-                      bool relu, const c10::optional<at::Tensor>& wt_packed) {
+                      bool relu, const OptTensor& wt_packed) {
   need(x, "x", 4);
-  need(w, "w", 4);
+  need(w, "w", 4, &x);
   const int64_t B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = w.size(0);
   TORCH_CHECK(w.size(1) == Cin && w.size(2) == 3 && w.size(3) == 3, "w must be (Cout, Cin, 3, 3)");
-  need(scale, "scale", 1);
-  need(shift, "shift", 1);
+  // one element per output channel of w (the engine pads the vectors with the weight)
+  const float* sc = vec_ptr(scale, Cout, "scale", x);
+  const float* sh = vec_ptr(shift, Cout, "shift", x);
+  TORCH_CHECK(sc && sh, "scale and shift must be defined");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto out = at::empty({B, H, W, Cout}, x.options());
   if ((Cout == 16 || Cout == 32 || Cout == 64) && Cin <= 16) {  // wave-uniform weights (scalar loads)
     at::Tensor wt;
-    if (wt_packed.has_value() && wt_packed->defined()) {
+    if (present(wt_packed)) {
       wt = *wt_packed;
-      need(wt, "wt", 4);
+      need(wt, "wt", 4, &x);
       TORCH_CHECK(wt.size(0) == Cin && wt.size(1) == 3 && wt.size(2) == 3 && wt.size(3) == Cout,
                   "wt must be (Cin, 3, 3, Cout)");
     } else {
       wt = w.permute({1, 2, 3, 0}).contiguous();  // [Cin][3][3][Cout]
     }
-    TP_CHECK_HIP(tp_conv_first_wave(x.data_ptr<float>(), wt.data_ptr<float>(), scale.data_ptr<float>(),
-                                    shift.data_ptr<float>(), out.data_ptr<float>(), (int)B, (int)Cin, (int)H, (int)W,
-                                    (int)Cout, relu ? 1 : 0, cur_stream()));
+    TP_CHECK_HIP(tp_conv_first_wave(x.data_ptr<float>(), wt.data_ptr<float>(), sc, sh, out.data_ptr<float>(), (int)B,
+                                    (int)Cin, (int)H, (int)W, (int)Cout, relu ? 1 : 0, cur_stream()));
     return out;
   }
-  TP_CHECK_HIP(tp_conv_first_direct(x.data_ptr<float>(), w.data_ptr<float>(), scale.data_ptr<float>(),
-                                    shift.data_ptr<float>(), out.data_ptr<float>(), (int)B, (int)Cin, (int)H, (int)W,
-                                    (int)Cout, relu ? 1 : 0, cur_stream()));
+  TP_CHECK_HIP(tp_conv_first_direct(x.data_ptr<float>(), w.data_ptr<float>(), sc, sh, out.data_ptr<float>(), (int)B,
+                                    (int)Cin, (int)H, (int)W, (int)Cout, relu ? 1 : 0, cur_stream()));
   return out;
 }
 
@@ -341,9 +257,9 @@ void pack_conv_weights_multi(const std::vector<at::Tensor>& ws, const std::vecto
 std::tuple<at::Tensor, at::Tensor> prefix_tri_operands(const at::Tensor& z, const at::Tensor& w, const at::Tensor& perm,
                                                        int64_t p0, int64_t cnt, int64_t Kc) {
   need(z, "z", 2);
-  need(w, "w", 2);
-  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == at::kInt && perm.is_contiguous() && perm.dim() == 1,
-              "perm must be a contiguous int32 GPU vector");
+  need(w, "w", 2, &z);
+  TORCH_CHECK(perm.is_cuda() && perm.device() == z.device() && perm.scalar_type() == at::kInt &&
+                  perm.is_contiguous() && perm.dim() == 1, "perm must be a contiguous int32 GPU vector on z's device");
   const int64_t B = z.size(0), C = z.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == C, "w must be (N, C) with z's C");
   TORCH_CHECK(cnt >= 1 && Kc >= cnt && Kc % 32 == 0, "need 1 <= cnt <= Kc, Kc % 32 == 0");
@@ -362,13 +278,13 @@ std::tuple<at::Tensor, at::Tensor> prefix_tri_operands(const at::Tensor& z, cons
 at::Tensor prefix_delta(const at::Tensor& T, const at::Tensor& wsub, const at::Tensor& neg_one, const at::Tensor& y0,
                         bool relu, double slope, int64_t cfg) {
   need(T, "T", 2);
-  need(wsub, "wsub", 2);
-  need(y0, "y0", 2);
+  need(wsub, "wsub", 2, &T);
+  need(y0, "y0", 2, &T);
   const int64_t M = T.size(0), Kc = T.size(1), N = wsub.size(0), B0 = y0.size(0);
   TORCH_CHECK(wsub.size(1) == Kc && y0.size(1) == N, "shape mismatch: T (M, Kc), wsub (N, Kc), y0 (B0, N)");
   TORCH_CHECK(Kc % 32 == 0 && N % 4 == 0 && M % B0 == 0, "need Kc % 32 == 0, N % 4 == 0, M % B0 == 0");
   TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
-  const float* no = opt_ptr(neg_one, N, "neg_one");
+  const float* no = opt_ptr(neg_one, N, "neg_one", T);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(T.device());
   auto out = at::empty({M, N}, T.options());
   TP_CHECK_HIP(tp_prefix_delta_gemm(T.data_ptr<float>(), wsub.data_ptr<float>(), no, y0.data_ptr<float>(), (int)M,
@@ -377,18 +293,11 @@ at::Tensor prefix_delta(const at::Tensor& T, const at::Tensor& wsub, const at::T
   return out;
 }
 
-int64_t wino_splits(int64_t splits, int64_t C) {
-  const int64_t chunks = C / 8;
-  splits = std::max<int64_t>(1, std::min<int64_t>(splits, chunks));
-  const int64_t per = (chunks + splits - 1) / splits;
-  return (chunks + per - 1) / per;
-}
-
 // fp32 images, or bf16 ones (the BF kernels; staged input modes only): returns the staged-flag bit
-int need_u(const at::Tensor& u, int64_t C, int64_t K) {
-  TORCH_CHECK(u.is_cuda() && u.is_contiguous() && u.dim() == 3 &&
+int need_u(const at::Tensor& u, int64_t C, int64_t K, const at::Tensor& like) {
+  TORCH_CHECK(u.is_cuda() && u.device() == like.device() && u.is_contiguous() && u.dim() == 3 &&
                   (u.scalar_type() == at::kFloat || u.scalar_type() == at::kBFloat16),
-              "u must be a contiguous float32 or bfloat16 GPU tensor (C/8, K/32, 4096)");
+              "u must be a contiguous float32 or bfloat16 tensor (C/8, K/32, 4096) on the other operands' device");
   TORCH_CHECK(C % 8 == 0 && K % 32 == 0 && u.size(0) == C / 8 && u.size(1) == K / 32 && u.size(2) == 4096,
               "u must be the Winograd U images (C/8, K/32, 4096) = (", C / 8, ", ", K / 32, ", 4096), got ",
               u.sizes());
@@ -396,87 +305,52 @@ int need_u(const at::Tensor& u, int64_t C, int64_t K) {
 }
 
 // Winograd F(2x2,3x3) forward: x (B,H,W,C) NHWC, u (16, C, K) from winograd_weights().
-std::tuple<at::Tensor, at::Tensor> conv_wino_fwd(const at::Tensor& x, const at::Tensor& u,
-                                                 const c10::optional<at::Tensor>& scale,
-                                                 const c10::optional<at::Tensor>& shift, bool relu, bool pool,
-                                                 int64_t splits, bool staged, const c10::optional<at::Tensor>& apoz) {
+std::tuple<at::Tensor, at::Tensor> conv_wino_fwd(const at::Tensor& x, const at::Tensor& u, const OptTensor& scale,
+                                                 const OptTensor& shift, bool relu, bool pool, int64_t splits,
+                                                 bool staged, const OptTensor& apoz) {
   need(x, "x", 4);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), K = u.size(1) * 32;
-  const int ubf = need_u(u, C, K);
+  const int ubf = need_u(u, C, K, x);
   TORCH_CHECK(!ubf || staged, "bf16 U images need the staged kernels");
   TORCH_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), "Winograd with pooling needs even H, W");
-  TORCH_CHECK(C % 8 == 0 && K % 32 == 0, "Winograd needs C % 8 == 0 and K % 32 == 0");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sc = opt_ptr(scale, K, "scale");
-  const float* sh = opt_ptr(shift, K, "shift");
-  at::Tensor out, am;
-  if (pool) {
-    out = at::empty({B, H / 2, W / 2, K}, x.options());
-    am = at::empty({B, H / 2, W / 2, K}, x.options().dtype(at::kByte));
-  } else {
-    out = at::empty({B, H, W, K}, x.options());
-  }
-  const int64_t sp = wino_splits(splits, C);
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * K}, x.options());
-  float* ap = nullptr;
-  if (apoz.has_value() && apoz->defined()) {
-    TORCH_CHECK(apoz->is_cuda() && apoz->scalar_type() == at::kFloat && apoz->is_contiguous() &&
-                    apoz->numel() == B * K, "apoz must be a contiguous float32 (B, K) tensor");
-    ap = apoz->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(scale, K, "scale", x);
+  const float* sh = opt_ptr(shift, K, "shift", x);
+  auto [out, am] = conv_out(x, B, H, W, K, pool);
+  const int64_t sp = norm_splits(splits, C / 8);
+  at::Tensor ws = splitk_ws(sp, B * H * W * K, x);
+  float* ap = count_ptr(apoz, B, K, x);
   TP_CHECK_HIP(tp_conv_wino(x.data_ptr<float>(), nullptr, static_cast<const float*>(u.data_ptr()), (int)B, (int)H,
                             (int)W, (int)C, (int)K, 0, pool ? EPI_FWD_POOL : EPI_FWD, (int)sp, (staged ? 1 : 0) | ubf,
-                            sc, sh, relu ? 1 : 0,
-                            out.data_ptr<float>(),
-                            pool ? am.data_ptr<uint8_t>() : nullptr, nullptr, nullptr, ap,
-                            sp > 1 ? ws.data_ptr<float>() : nullptr, 0, cur_stream()));
+                            sc, sh, relu ? 1 : 0, out.data_ptr<float>(), pool ? am.data_ptr<uint8_t>() : nullptr,
+                            nullptr, nullptr, ap, ptr_or_null(ws), 0, cur_stream()));
   return {out, am};
 }
 
 // Winograd dgrad with the conv_dgrad epilogue contract; ut = winograd_weights of the
 // flipped/transposed kernel, (16, Cout, Cin).
-at::Tensor conv_wino_dgrad(const at::Tensor& g, const c10::optional<at::Tensor>& g_argmax, const at::Tensor& ut,
-                           const at::Tensor& act, const c10::optional<at::Tensor>& bn_scale,
-                           const c10::optional<at::Tensor>& taylor, bool want_out, int64_t splits, bool staged,
-                           int64_t tay_mode) {
+at::Tensor conv_wino_dgrad(const at::Tensor& g, const OptTensor& g_argmax, const at::Tensor& ut, const at::Tensor& act,
+                           const OptTensor& bn_scale, const OptTensor& taylor, bool want_out, int64_t splits,
+                           bool staged, int64_t tay_mode) {
   need(g, "g", 4);
-  need(act, "act", 4);
-  const bool unpool = g_argmax.has_value() && g_argmax->defined();
+  need(act, "act", 4, &g);
   const int64_t B = act.size(0), H = act.size(1), W = act.size(2), Cin = act.size(3), Cout = g.size(3);
-  const int ubf = need_u(ut, Cout, Cin);
+  const int ubf = need_u(ut, Cout, Cin, g);
   TORCH_CHECK(!ubf || staged, "bf16 U images need the staged kernels");
-  if (unpool) {
-    TORCH_CHECK(g.size(1) * 2 == H && g.size(2) * 2 == W, "pooled grad shape mismatch");
-    TORCH_CHECK(g_argmax->scalar_type() == at::kByte && g_argmax->sizes() == g.sizes() && g_argmax->is_contiguous(),
-                "g_argmax must be uint8 with g's shape");
-  } else {
-    TORCH_CHECK(g.size(1) == H && g.size(2) == W, "grad shape mismatch");
-  }
-  TORCH_CHECK(g.size(0) == B, "batch mismatch");
-  TORCH_CHECK(!unpool || (H % 2 == 0 && W % 2 == 0), "Winograd with unpooling needs even H, W");
-  TORCH_CHECK(Cout % 8 == 0 && Cin % 32 == 0, "Winograd dgrad needs Cout % 8 == 0 and Cin % 32 == 0");
+  const uint8_t* am = pooled_grad(g, g_argmax, B, H, W);  // (pooled: H, W are even)
+  const int tm = tay_mode_arg(tay_mode, 2);               // the launcher passes it on unchecked
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale");
-  float* tay = nullptr;
-  if (taylor.has_value() && taylor->defined()) {
-    const int64_t R = tp_wino_taylor_slots((int)H, (int)W);
-    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
-                    taylor->numel() % (B * Cin) == 0 && taylor->numel() >= R * B * Cin,
-                "taylor must be a contiguous float32 (R', B, Cin) GPU tensor with R' >= ", R,
-                " partial slots (winograd_taylor_slots)");
-    tay = taylor->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale", g);
+  // at least winograd_taylor_slots(H, W) partial slots
+  float* tay = taylor_ptr(taylor, tp_wino_taylor_slots((int)H, (int)W), false, B, Cin, g);
   at::Tensor out;
   if (want_out) out = at::empty({B, H, W, Cin}, g.options());
-  const int64_t sp = wino_splits(splits, Cout);
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * Cin}, g.options());
-  TP_CHECK_HIP(tp_conv_wino(g.data_ptr<float>(), unpool ? g_argmax->data_ptr<uint8_t>() : nullptr,
-                            static_cast<const float*>(ut.data_ptr()), (int)B, (int)H, (int)W, (int)Cout, (int)Cin,
-                            unpool ? 1 : 0, EPI_BWD, (int)sp, (staged ? 1 : 0) | ubf, sc, nullptr, 0, want_out ? out.data_ptr<float>() : nullptr, nullptr,
-                            act.data_ptr<float>(), tay, nullptr, sp > 1 ? ws.data_ptr<float>() : nullptr,
-                            (int)tay_mode, cur_stream()));
+  const int64_t sp = norm_splits(splits, Cout / 8);
+  at::Tensor ws = splitk_ws(sp, B * H * W * Cin, g);
+  TP_CHECK_HIP(tp_conv_wino(g.data_ptr<float>(), am, static_cast<const float*>(ut.data_ptr()), (int)B, (int)H, (int)W,
+                            (int)Cout, (int)Cin, am ? 1 : 0, EPI_BWD, (int)sp, (staged ? 1 : 0) | ubf, sc, nullptr, 0,
+                            ptr_or_null(out), nullptr, act.data_ptr<float>(), tay, nullptr, ptr_or_null(ws), tm,
+                            cur_stream()));
   return out;
 }
 
@@ -499,7 +373,11 @@ at::Tensor wino4_weights(const at::Tensor& w, bool flip_t, int64_t K, int64_t C)
   return u;
 }
 
-void need_u4(const at::Tensor& u, int64_t C, int64_t K);
+void need_u4(const at::Tensor& u, int64_t C, int64_t K, const at::Tensor& like) {
+  need(u, "u", 3, &like);
+  TORCH_CHECK(C % 8 == 0 && K % 32 == 0 && u.size(0) == C / 8 && u.size(1) == K / 32 && u.size(2) == tp_wino4_u_img(),
+              "u must be the F(4x4) U images (C/8, K/32, ", tp_wino4_u_img(), "), got ", u.sizes());
+}
 
 // F(4x4) U images of many 3x3 weights in one launch: us[i] <- ws[i] per cfg[3i:3i+3] = (K, C,
 // flip_t) (the padded GEMM widths, as wino4_weights). ws may be strided (channels_last).
@@ -522,8 +400,7 @@ void wino4_weights_multi(const std::vector<at::Tensor>& ws, const std::vector<at
     TORCH_CHECK(K > 0 && C > 0 && K % 32 == 0 && C % 8 == 0 &&
                     (flip ? (w.size(0) <= C && w.size(1) <= K) : (w.size(0) <= K && w.size(1) <= C)),
                 "wino4_weights_multi: bad padded widths");
-    need_u4(us[i], C, K);
-    TORCH_CHECK(us[i].device() == w.device(), "wino4_weights_multi: u on w's device");
+    need_u4(us[i], C, K, w);
     int64_t* d = h + i * D;
     d[0] = reinterpret_cast<int64_t>(w.data_ptr<float>());
     d[1] = reinterpret_cast<int64_t>(us[i].data_ptr<float>());
@@ -544,20 +421,12 @@ void wino4_weights_multi(const std::vector<at::Tensor>& ws, const std::vector<at
                                       (long long)total, cur_stream()));
 }
 
-void need_u4(const at::Tensor& u, int64_t C, int64_t K) {
-  need(u, "u", 3);
-  TORCH_CHECK(C % 8 == 0 && K % 32 == 0 && u.size(0) == C / 8 && u.size(1) == K / 32 && u.size(2) == tp_wino4_u_img(),
-              "u must be the F(4x4) U images (C/8, K/32, ", tp_wino4_u_img(), "), got ", u.sizes());
-}
-
-std::tuple<at::Tensor, at::Tensor> conv_wino4_fwd(const at::Tensor& x, const at::Tensor& u,
-                                                  const c10::optional<at::Tensor>& scale,
-                                                  const c10::optional<at::Tensor>& shift, bool relu, bool pool,
-                                                  const c10::optional<at::Tensor>& apoz, int64_t splits,
-                                                  int64_t variant, int64_t ko) {
+std::tuple<at::Tensor, at::Tensor> conv_wino4_fwd(const at::Tensor& x, const at::Tensor& u, const OptTensor& scale,
+                                                  const OptTensor& shift, bool relu, bool pool, const OptTensor& apoz,
+                                                  int64_t splits, int64_t variant, int64_t ko) {
   need(x, "x", 4);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), Kc = u.size(1) * 32;
-  need_u4(u, C, Kc);
+  need_u4(u, C, Kc, x);
   TORCH_CHECK(tp_wino4_ok((int)H, (int)W, (int)C, (int)Kc), "F(4x4) Winograd needs square 4/8/16/32 (or, split-points "
               "variant 3 without pooling, 56/28/14/7) maps, C % 8 == 0, "
               "K % 32 == 0; got ", x.sizes(), " K=", Kc);
@@ -566,78 +435,54 @@ std::tuple<at::Tensor, at::Tensor> conv_wino4_fwd(const at::Tensor& x, const at:
   TORCH_CHECK(K % 4 == 0 && K <= Kc && K > Kc - 32, "ko must be a multiple of 4 in (K - 32, K]; got ko=", ko, " K=", Kc);
   TORCH_CHECK(K == Kc || splits <= 1, "ko < K needs one K pass (splits=1)");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sc = opt_ptr(scale, K, "scale");
-  const float* sh = opt_ptr(shift, K, "shift");
-  at::Tensor out, am;
-  if (pool) {
-    out = at::empty({B, H / 2, W / 2, K}, x.options());
-    am = at::empty({B, H / 2, W / 2, K}, x.options().dtype(at::kByte));
-  } else {
-    out = at::empty({B, H, W, K}, x.options());
-  }
-  float* ap = nullptr;
-  if (apoz.has_value() && apoz->defined()) {
-    TORCH_CHECK(apoz->is_cuda() && apoz->scalar_type() == at::kFloat && apoz->is_contiguous() &&
-                    apoz->numel() == B * K, "apoz must be a contiguous float32 (B, K) tensor");
-    ap = apoz->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(scale, K, "scale", x);
+  const float* sh = opt_ptr(shift, K, "shift", x);
+  auto [out, am] = conv_out(x, B, H, W, K, pool);
+  float* ap = count_ptr(apoz, B, K, x);
+  // (clamped only: the launcher drops the empty splits and the slabs of the rest still fit)
   const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, C / 8));
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * K}, x.options());
+  at::Tensor ws = splitk_ws(sp, B * H * W * K, x);
   TP_CHECK_HIP(tp_conv_wino4(x.data_ptr<float>(), u.data_ptr<float>(), (int)B, (int)H, (int)C, (int)Kc,
                              pool ? EPI_FWD_POOL : EPI_FWD, sc, sh, relu ? 1 : 0, out.data_ptr<float>(),
                              pool ? am.data_ptr<uint8_t>() : nullptr, nullptr, nullptr, ap, 0, (int)sp,
-                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), nullptr, (int)K));
+                             ptr_or_null(ws), (int)variant, cur_stream(), nullptr, (int)K));
   return {out, am};
 }
 
 // F(4x4) dgrad with the conv_wino_dgrad epilogue contract (input: the unpooled grad). unpool_am
 // (B, H, W, Cin) uint8, with want_out and one K pass: the output is written unpooled through those
 // 2x2-pool argmax bytes at (B, 2H, 2W, Cin) — the operand of the previous layer's data gradient
-at::Tensor conv_wino4_dgrad(const at::Tensor& g, const at::Tensor& ut, const at::Tensor& act,
-                            const c10::optional<at::Tensor>& bn_scale, const c10::optional<at::Tensor>& taylor,
-                            bool want_out, int64_t tay_mode, int64_t splits, int64_t variant,
-                            const c10::optional<at::Tensor>& unpool_am) {
+at::Tensor conv_wino4_dgrad(const at::Tensor& g, const at::Tensor& ut, const at::Tensor& act, const OptTensor& bn_scale,
+                            const OptTensor& taylor, bool want_out, int64_t tay_mode, int64_t splits, int64_t variant,
+                            const OptTensor& unpool_am) {
   need(g, "g", 4);
-  need(act, "act", 4);
+  need(act, "act", 4, &g);
   // Cin: the stored input-gradient channels (act's width); the U images cover Cin rounded up to 32
   const int64_t B = act.size(0), H = act.size(1), W = act.size(2), Cin = act.size(3), Cout = g.size(3);
   const int64_t Kc = ut.dim() == 3 ? ut.size(1) * 32 : 0;
-  need_u4(ut, Cout, Kc);
+  need_u4(ut, Cout, Kc, g);
   TORCH_CHECK(Cin % 4 == 0 && Cin <= Kc && Cin > Kc - 32, "act width must be the U images' output width up to its "
               "32-granule; got ", Cin, " vs ", Kc);
   TORCH_CHECK(g.size(0) == B && g.size(1) == H && g.size(2) == W, "grad shape mismatch");
   TORCH_CHECK(tp_wino4_ok((int)H, (int)W, (int)Cout, (int)Kc), "F(4x4) dgrad needs square 4/8/16/32/56/28/14/7 maps, "
               "Cout % 8 == 0, Cin % 32 == 0");
+  const int tm = tay_mode_arg(tay_mode, 2);  // the launcher passes it on unchecked
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale");
-  float* tay = nullptr;
-  if (taylor.has_value() && taylor->defined()) {
-    const int64_t R = tp_wino4_taylor_slots((int)H);
-    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
-                    taylor->numel() % (B * Cin) == 0 && taylor->numel() >= R * B * Cin,
-                "taylor must be a contiguous float32 (R', B, Cin) GPU tensor with R' >= ", R, " partial slots");
-    tay = taylor->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(bn_scale, Cin, "bn_scale", g);
+  float* tay = taylor_ptr(taylor, tp_wino4_taylor_slots((int)H), false, B, Cin, g);
   const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, Cout / 8));
   TORCH_CHECK(Cin == Kc || sp == 1, "an unpadded output width needs one K pass (splits=1)");
   const uint8_t* unp = nullptr;
-  if (unpool_am.has_value() && unpool_am->defined()) {
-    const auto& m = *unpool_am;
+  if (present(unpool_am)) {  // one byte per element of act
     TORCH_CHECK(want_out && sp == 1, "fused unpooling needs want_out and one K pass (splits=1)");
-    TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kByte && m.is_contiguous() && m.dim() == 4 && m.size(0) == B &&
-                    m.size(1) == H && m.size(2) == W && m.size(3) == Cin,
-                "unpool_am must be contiguous uint8 (B, H, W, Cin) argmax bytes on the GPU");
-    unp = m.data_ptr<uint8_t>();
+    unp = argmax_ptr(*unpool_am, "unpool_am", act);
   }
   at::Tensor out;
   if (want_out) out = unp ? at::empty({B, 2 * H, 2 * W, Cin}, g.options()) : at::empty({B, H, W, Cin}, g.options());
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * H * W * Cin}, g.options());
+  at::Tensor ws = splitk_ws(sp, B * H * W * Cin, g);
   TP_CHECK_HIP(tp_conv_wino4(g.data_ptr<float>(), ut.data_ptr<float>(), (int)B, (int)H, (int)Cout, (int)Kc,
-                             EPI_BWD, sc, nullptr, 0, want_out ? out.data_ptr<float>() : nullptr, nullptr,
-                             act.data_ptr<float>(), tay, nullptr, (int)tay_mode, (int)sp,
-                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)variant, cur_stream(), unp, (int)Cin));
+                             EPI_BWD, sc, nullptr, 0, ptr_or_null(out), nullptr, act.data_ptr<float>(), tay, nullptr,
+                             tm, (int)sp, ptr_or_null(ws), (int)variant, cur_stream(), unp, (int)Cin));
   return out;
 }
 
@@ -645,69 +490,43 @@ at::Tensor conv_wino4_dgrad(const at::Tensor& g, const at::Tensor& ut, const at:
 
 int64_t wino_taylor_slots(int64_t H, int64_t W) { return tp_wino_taylor_slots((int)H, (int)W); }
 
-// Stream-K fixup workspace of a GEN conv launch whose cfg carries the stream-K flag (32): undefined
-// when the flag is absent or stream-K does not apply at this shape (the launcher then runs the
-// data-parallel grid).
-static constexpr int64_t kCfgSK = 32;
-static at::Tensor sk_workspace(int64_t cfg, int64_t ks, bool transposed, bool tay, int64_t M, int64_t N,
-                        const at::TensorOptions& o) {
-  if (cfg < 0 || !(cfg & kCfgSK)) return at::Tensor();
-  const long long n = tp_conv_sk_ws_floats((int)(cfg & ~kCfgSK), (int)ks, transposed ? 1 : 0, tay ? 1 : 0, (int)M,
-                                           (int)N);
-  return n > 0 ? at::empty({(int64_t)n}, o) : at::Tensor();
+// Operands and geometry of a GEN forward conv (conv_gen, conv_gen_stats): x NHWC (B,H,W,Cin), w (Cout, K).
+struct GenShape {
+  int64_t B, H, W, Cin, Cout, Ho, Wo;
+};
+static GenShape gen_shape(const at::Tensor& x, const at::Tensor& w, int64_t ks, int64_t stride, int64_t pad) {
+  need(x, "x", 4);
+  need(w, "w", 2, &x);
+  const int64_t H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = w.size(0);
+  TORCH_CHECK((Cin % 4 == 0 && Cin >= 8 && (ks == 1 || ks == 3 || ks == 5)) ||
+                  (Cin == 4 && (ks == 3 || ks == 5 || ks == 7)),
+              "GEN convs support ks 1/3/5 with Cin % 4 == 0 (>= 8), or ks 3/5/7 with a 4-channel input");
+  TORCH_CHECK(w.size(1) == tp_conv_gen_k((int)ks, (int)Cin), "weight K mismatch");
+  TORCH_CHECK(stride >= 1 && pad >= 0, "bad stride/pad");
+  TORCH_CHECK(Cout % 4 == 0, "GEN convs need Cout % 4 == 0");
+  return {x.size(0), H, W, Cin, Cout, (H + 2 * pad - ks) / stride + 1, (W + 2 * pad - ks) / stride + 1};
 }
 
 // General strided conv forward (ResNet): x NHWC (B,H,W,Cin) with Cin % 32 == 0 (ks 1 or 3) or
 // Cin == 4 (ks 7, padded stem input); w (Cout, K) with K = conv_gen_k(ks, Cin), k = (kh,kw,ci).
 // Epilogue: out = relu?(acc*scale + shift + res); apoz (B, Cout) += count(out > 0).
-at::Tensor conv_gen(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& scale,
-                    const c10::optional<at::Tensor>& shift, bool relu, const c10::optional<at::Tensor>& res,
-                    const c10::optional<at::Tensor>& apoz, int64_t ks, int64_t stride, int64_t pad, int64_t cfg,
+at::Tensor conv_gen(const at::Tensor& x, const at::Tensor& w, const OptTensor& scale, const OptTensor& shift, bool relu,
+                    const OptTensor& res, const OptTensor& apoz, int64_t ks, int64_t stride, int64_t pad, int64_t cfg,
                     int64_t splits) {
-  need(x, "x", 4);
-  need(w, "w", 2);
-  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = w.size(0);
-  TORCH_CHECK((Cin % 4 == 0 && Cin >= 8 && (ks == 1 || ks == 3 || ks == 5)) ||
-                  (Cin == 4 && (ks == 3 || ks == 5 || ks == 7)),
-              "conv_gen supports ks 1/3/5 with Cin % 4 == 0 (>= 8), or ks 3/5/7 with a 4-channel input");
-  TORCH_CHECK(w.size(1) == tp_conv_gen_k((int)ks, (int)Cin), "weight K mismatch");
-  TORCH_CHECK(stride >= 1 && pad >= 0, "bad stride/pad");
-  TORCH_CHECK(Cout % 4 == 0, "conv_gen needs Cout % 4 == 0");
-  const int64_t Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+  const auto [B, H, W, Cin, Cout, Ho, Wo] = gen_shape(x, w, ks, stride, pad);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sc = opt_ptr(scale, Cout, "scale");
-  const float* sh = opt_ptr(shift, Cout, "shift");
-  const float* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    need(*res, "res", 4);
-    TORCH_CHECK(res->size(0) == B && res->size(1) == Ho && res->size(2) == Wo && res->size(3) == Cout,
-                "res must be (B, Ho, Wo, Cout)");
-    rp = res->data_ptr<float>();
-  }
-  float* ap = nullptr;
-  if (apoz.has_value() && apoz->defined()) {
-    TORCH_CHECK(apoz->is_cuda() && apoz->scalar_type() == at::kFloat && apoz->is_contiguous() &&
-                    apoz->numel() == B * Cout, "apoz must be a contiguous float32 (B, Cout) tensor");
-    ap = apoz->data_ptr<float>();
-  }
+  const float* sc = opt_ptr(scale, Cout, "scale", x);
+  const float* sh = opt_ptr(shift, Cout, "shift", x);
+  const float* rp = res_ptr(res, B, Ho, Wo, Cout, 1, x);
+  float* ap = count_ptr(apoz, B, Cout, x);
   auto out = at::empty({B, Ho, Wo, Cout}, x.options());
-  const int64_t K = w.size(1), kt = K / 32;
-  int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, kt));
-  const int64_t per = (kt + sp - 1) / sp;
-  sp = (kt + per - 1) / per;
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * Ho * Wo * Cout}, x.options());
-  int64_t cf = cfg;
-  if (sp == 1 && Cin != 4) {
-    ws = sk_workspace(cfg, ks, false, false, B * Ho * Wo, Cout, x.options());
-    if (!ws.defined()) cf = cfg & ~kCfgSK;
-  } else if (cfg >= 0) {
-    cf = cfg & ~kCfgSK;
-  }
+  const int64_t sp = norm_splits(splits, w.size(1) / 32);
+  SkPlan sk = sk_plan(sp == 1 && Cin != 4, cfg, ks, false, B * Ho * Wo, Cout, x);
+  if (sp > 1) sk.ws = splitk_ws(sp, B * Ho * Wo * Cout, x);
   TP_CHECK_HIP(tp_conv_gen(x.data_ptr<float>(), w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)cf, (int)sp, sc, sh, relu ? 1 : 0, rp, 1,
-                           nullptr, ap, out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr,
-                           nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, cur_stream()));
+                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)sk.cfg, (int)sp, sc, sh, relu ? 1 : 0, rp, 1,
+                           nullptr, ap, out.data_ptr<float>(), ptr_or_null(sk.ws), nullptr, nullptr, 0, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, cur_stream()));
   return out;
 }
 
@@ -752,12 +571,12 @@ std::tuple<at::Tensor, at::Tensor> maxpool2_nhwc(const at::Tensor& x) {
 // inverse of maxpool2_nhwc: scatter the pooled gradient to the argmax positions
 at::Tensor unpool2_nhwc(const at::Tensor& g, const at::Tensor& am) {
   need(g, "g", 4);
-  TORCH_CHECK(am.scalar_type() == at::kByte && am.sizes() == g.sizes() && am.is_contiguous(), "am must match g");
+  const uint8_t* amp = argmax_ptr(am, "am", g);
   const int64_t B = g.size(0), H = g.size(1) * 2, W = g.size(2) * 2, C = g.size(3);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   auto out = at::empty({B, H, W, C}, g.options());
-  TP_CHECK_HIP(tp_unpool2_nhwc(g.data_ptr<float>(), am.data_ptr<uint8_t>(), out.data_ptr<float>(), (int)B, (int)H,
-                               (int)W, (int)C, cur_stream()));
+  TP_CHECK_HIP(tp_unpool2_nhwc(g.data_ptr<float>(), amp, out.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C,
+                               cur_stream()));
   return out;
 }
 
@@ -778,12 +597,11 @@ at::Tensor nchw_to_nhwc_pad(const at::Tensor& x, int64_t Cp) {
 // transposed: output (B, Ho, Wo, N) gathers y pixel ((oh + pad - kh)/stride, ...) (strided
 // conv dgrad); otherwise a plain stride-1 conv of g (1x1, or 3x3 with flipped taps).
 // Epilogue: v (+ res, res_stride-scattered) then out = mask > 0 ? v : 0 when mask is given.
-at::Tensor conv_gen_bwd(const at::Tensor& g, const at::Tensor& wt, const c10::optional<at::Tensor>& res,
-                        int64_t res_stride, const c10::optional<at::Tensor>& mask, int64_t ks, int64_t stride,
-                        int64_t pad, int64_t Ho, int64_t Wo, bool transposed, int64_t cfg, int64_t splits,
-                        const c10::optional<at::Tensor>& taylor, int64_t tay_mode) {
+at::Tensor conv_gen_bwd(const at::Tensor& g, const at::Tensor& wt, const OptTensor& res, int64_t res_stride,
+                        const OptTensor& mask, int64_t ks, int64_t stride, int64_t pad, int64_t Ho, int64_t Wo,
+                        bool transposed, int64_t cfg, int64_t splits, const OptTensor& taylor, int64_t tay_mode) {
   need(g, "g", 4);
-  need(wt, "wt", 2);
+  need(wt, "wt", 2, &g);
   const int64_t B = g.size(0), H = g.size(1), W = g.size(2), C = g.size(3), N = wt.size(0);
   TORCH_CHECK(C % 4 == 0 && C >= 8 && (ks == 1 || ks == 3 || (ks == 5 && !transposed)),
               "conv_gen_bwd needs C % 4 == 0 (>= 8) and ks 1/3 (5 for stride-1 convs)");
@@ -797,29 +615,15 @@ at::Tensor conv_gen_bwd(const at::Tensor& g, const at::Tensor& wt, const c10::op
     TORCH_CHECK((Ho + 2 * pad - ks) / stride + 1 == H && (Wo + 2 * pad - ks) / stride + 1 == W,
                 "Ho/Wo inconsistent with the forward conv geometry");
   }
+  // the kernel tests tay_mode for zero only: 0 Taylor, 1 Sensitivity (the launcher passes it on unchecked)
+  const int tm = tay_mode_arg(tay_mode, 1);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const float* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    need(*res, "res", 4);
-    const int64_t Hr = (Ho + res_stride - 1) / res_stride, Wr = (Wo + res_stride - 1) / res_stride;
-    TORCH_CHECK(res->size(0) == B && res->size(1) == Hr && res->size(2) == Wr && res->size(3) == N,
-                "res must be (B, ceil(Ho/s), ceil(Wo/s), N)");
-    rp = res->data_ptr<float>();
-  }
-  const float* mp = nullptr;
-  if (mask.has_value() && mask->defined()) {
-    need(*mask, "mask", 4);
-    TORCH_CHECK(mask->size(0) == B && mask->size(1) == Ho && mask->size(2) == Wo && mask->size(3) == N,
-                "mask must be (B, Ho, Wo, N)");
-    mp = mask->data_ptr<float>();
-  }
+  const float* rp = res_ptr(res, B, Ho, Wo, N, res_stride, g);
+  const float* mp = nhwc_ptr(mask, "mask", B, Ho, Wo, N, g);
   auto out = at::empty({B, Ho, Wo, N}, g.options());
-  const int64_t kt = wt.size(1) / 32;
-  int64_t sp = transposed ? 1 : std::max<int64_t>(1, std::min<int64_t>(splits, kt));
-  const int64_t per = (kt + sp - 1) / sp;
-  sp = (kt + per - 1) / per;
+  const int64_t sp = transposed ? 1 : norm_splits(splits, wt.size(1) / 32);
   float* tp_ = nullptr;
-  if (taylor.has_value() && taylor->defined()) {
+  if (present(taylor)) {
     // fused Taylor / Sensitivity partials (R, B, N) of the masked output: a 1x1 stride-1 dgrad
     // (one K pass), or a transposed 3x3 stride-2 one at even Ho / Wo (the parity row order: one
     // slot range per stride phase, R = 4 x the slots of an Ho/2 x Wo/2 group)
@@ -829,38 +633,19 @@ at::Tensor conv_gen_bwd(const at::Tensor& g, const at::Tensor& wt, const c10::op
     TORCH_CHECK(((!transposed && ks == 1) || t3) && mp != nullptr && sp == 1 && R > 0,
                 "conv_gen_bwd taylor partials need a mask and a 1x1 stride-1 dgrad (one K pass) or a transposed "
                 "3x3 stride-2 dgrad at even output size, and a tile config spanning <= 4 row groups");
-    TORCH_CHECK(taylor->is_cuda() && taylor->scalar_type() == at::kFloat && taylor->is_contiguous() &&
-                    taylor->numel() == (int64_t)R * B * N,
-                "taylor must be a contiguous float32 (R, B, N) GPU tensor with R = ", R);
-    tp_ = taylor->data_ptr<float>();
+    tp_ = taylor_ptr(taylor, R, true, B, N, g);
   }
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * B * Ho * Wo * N}, g.options());
-  int64_t cf = cfg;
-  if (sp == 1 && !transposed) {
-    ws = sk_workspace(cfg, ks, false, tp_ != nullptr, B * Ho * Wo, N, g.options());
-    if (!ws.defined()) cf = cfg & ~kCfgSK;
-  } else if (cfg >= 0) {
-    cf = cfg & ~kCfgSK;
-  }
+  SkPlan sk = sk_plan(sp == 1 && !transposed, cfg, ks, tp_ != nullptr, B * Ho * Wo, N, g);
+  if (sp > 1) sk.ws = splitk_ws(sp, B * Ho * Wo * N, g);
   TP_CHECK_HIP(tp_conv_gen(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N,
-                           (int)ks, (int)stride, (int)pad, transposed ? 1 : 0, (int)Ho, (int)Wo, (int)cf, (int)sp,
+                           (int)ks, (int)stride, (int)pad, transposed ? 1 : 0, (int)Ho, (int)Wo, (int)sk.cfg, (int)sp,
                            nullptr, nullptr, 0, rp, (int)res_stride, mp, nullptr, out.data_ptr<float>(),
-                           ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, tp_, (int)tay_mode, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, cur_stream()));
+                           ptr_or_null(sk.ws), nullptr, tp_, tm, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           cur_stream()));
   return out;
 }
 
 int64_t conv_gen_tay_slots(int64_t cfg, int64_t HWo) { return tp_conv_gen_tay_slots((int)cfg, (int)HWo); }
-
-static const uint8_t* bit_mask_ptr(const c10::optional<at::Tensor>& t, int64_t elems, const at::Tensor& like,
-                                   const char* what) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kByte && t->is_contiguous() && t->numel() == (elems + 3) / 4 &&
-                  t->device() == like.device(),
-              what, " must be a ReLU bit mask of ceil(elements / 4) uint8 on the device");
-  return t->data_ptr<uint8_t>();
-}
 
 // Data gradient of a 1x1 stride-1 conv (the training path's residual-block conv1) with the two
 // fusions of a bottleneck's backward (tp_conv_gen):
@@ -868,51 +653,35 @@ static const uint8_t* bit_mask_ptr(const c10::optional<at::Tensor>& t, int64_t e
 //   bn_y / bn_mean / bn_invstd (/ bn_bits): the output gradient reaches a BatchNorm (+ ReLU) whose
 //     backward statistics (sum gm, sum gm * xhat) come back per M tile, [tiles][2][N] fp64.
 // Returns (dx (B, H, W, N), tile statistics or an empty tensor).
-std::tuple<at::Tensor, at::Tensor> conv_gen_bwd_bn(const at::Tensor& g, const at::Tensor& wt,
-                                                   const c10::optional<at::Tensor>& res, int64_t res_stride,
-                                                   const c10::optional<at::Tensor>& res_bits,
-                                                   const c10::optional<at::Tensor>& bn_y,
-                                                   const c10::optional<at::Tensor>& bn_mean,
-                                                   const c10::optional<at::Tensor>& bn_invstd,
-                                                   const c10::optional<at::Tensor>& bn_bits, int64_t cfg) {
+std::tuple<at::Tensor, at::Tensor> conv_gen_bwd_bn(const at::Tensor& g, const at::Tensor& wt, const OptTensor& res,
+                                                   int64_t res_stride, const OptTensor& res_bits,
+                                                   const OptTensor& bn_y, const OptTensor& bn_mean,
+                                                   const OptTensor& bn_invstd, const OptTensor& bn_bits, int64_t cfg) {
   need(g, "g", 4);
-  need(wt, "wt", 2);
+  need(wt, "wt", 2, &g);
   const int64_t B = g.size(0), H = g.size(1), W = g.size(2), C = g.size(3), N = wt.size(0), M = B * H * W;
   TORCH_CHECK(C % 4 == 0 && C >= 8 && N % 4 == 0, "conv_gen_bwd_bn needs C % 4 == 0 (>= 8) and N % 4 == 0");
   TORCH_CHECK(wt.size(1) == tp_conv_gen_k(1, (int)C), "wt must be (N, ceil32(C))");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  TORCH_CHECK(res_stride >= 1, "res_stride must be >= 1");
-  const float* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    need(*res, "res", 4);
-    const int64_t Hr = (H + res_stride - 1) / res_stride, Wr = (W + res_stride - 1) / res_stride;
-    TORCH_CHECK(res->size(0) == B && res->size(1) == Hr && res->size(2) == Wr && res->size(3) == N,
-                "res must be (B, ceil(H/s), ceil(W/s), N)");
-    rp = res->data_ptr<float>();
-  }
+  const float* rp = res_ptr(res, B, H, W, N, res_stride, g);
   const uint8_t* rb = bit_mask_ptr(res_bits, M * N, g, "res_bits");
   TORCH_CHECK(!rb || (rp && res_stride == 1), "res_bits needs a stride-1 res");
-  const float* yp = nullptr;
+  const float* yp = nhwc_ptr(bn_y, "bn_y", B, H, W, N, g);
   at::Tensor part;
-  if (bn_y.has_value() && bn_y->defined()) {
-    need(*bn_y, "bn_y", 4);
-    TORCH_CHECK(bn_y->size(0) == B && bn_y->size(1) == H && bn_y->size(2) == W && bn_y->size(3) == N,
-                "bn_y must be (B, H, W, N)");
-    yp = bn_y->data_ptr<float>();
-    part = at::empty({(M + tp_conv_tile_m((int)cfg) - 1) / tp_conv_tile_m((int)cfg), 2, N},
-                     g.options().dtype(at::kDouble));
+  if (yp) {
+    const int64_t tm = tp_conv_tile_m((int)cfg);
+    part = at::empty({(M + tm - 1) / tm, 2, N}, g.options().dtype(at::kDouble));
   }
-  const float* mp = yp ? opt_ptr(bn_mean, N, "bn_mean") : nullptr;
-  const float* ip = yp ? opt_ptr(bn_invstd, N, "bn_invstd") : nullptr;
+  const float* mp = yp ? opt_ptr(bn_mean, N, "bn_mean", g) : nullptr;
+  const float* ip = yp ? opt_ptr(bn_invstd, N, "bn_invstd", g) : nullptr;
   TORCH_CHECK(!yp || (mp && ip), "bn_y needs bn_mean and bn_invstd");
   const uint8_t* bb = yp ? bit_mask_ptr(bn_bits, M * N, g, "bn_bits") : nullptr;
   auto out = at::empty({B, H, W, N}, g.options());
-  at::Tensor ws = sk_workspace(cfg, 1, false, false, M, N, g.options());
-  const int64_t cf = ws.defined() || cfg < 0 ? cfg : cfg & ~kCfgSK;
+  const SkPlan sk = sk_plan(true, cfg, 1, false, M, N, g);
   TP_CHECK_HIP(tp_conv_gen(g.data_ptr<float>(), wt.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)N, 1, 1,
-                           0, 0, 0, 0, (int)cf, 1, nullptr, nullptr, 0, rp, (int)res_stride, nullptr, nullptr,
-                           out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
-                           yp ? part.data_ptr<double>() : nullptr, nullptr, 0, rb, yp, mp, ip, bb, cur_stream()));
+                           0, 0, 0, 0, (int)sk.cfg, 1, nullptr, nullptr, 0, rp, (int)res_stride, nullptr, nullptr,
+                           out.data_ptr<float>(), ptr_or_null(sk.ws), yp ? part.data_ptr<double>() : nullptr, nullptr,
+                           0, rb, yp, mp, ip, bb, cur_stream()));
   return {out, part};
 }
 
@@ -924,13 +693,13 @@ int64_t conv_sk_ws(int64_t cfg, int64_t ks, bool tay, int64_t M, int64_t N) {
 
 // Weight gradient: g (B, Ho, Wo, Cout) and x (B, H, W, Cin) NHWC -> dW (Cout, Kpad) with column
 // k = (kh, kw, ci) (Kpad = ks*ks*Cin rounded up to 32; padded columns are zero).
-// ``out`` (optional): the parameter-shaped gradient (Cout_r, Cin_r, ks, ks), any strides, written
-// directly (real channels only); the (Cout, Kpad) GEMM result is then not materialised and an
+// ``out`` (optional): the parameter-shaped gradient (Cout_r, Cin_r, ks, ks), any positive strides,
+// written directly (real channels only); the (Cout, Kpad) GEMM result is then not materialised and an
 // empty tensor is returned.
 at::Tensor conv_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t ks, int64_t stride, int64_t pad, int64_t cfg,
-                      int64_t splits, const c10::optional<at::Tensor>& out) {
+                      int64_t splits, const OptTensor& out) {
   need(g, "g", 4);
-  need(x, "x", 4);
+  need(x, "x", 4, &g);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = g.size(3);
   TORCH_CHECK(Cin % 4 == 0 && Cout % 4 == 0, "conv_wgrad needs Cin % 4 == 0 and Cout % 4 == 0");
   TORCH_CHECK(ks >= 1 && stride >= 1 && pad >= 0, "bad conv geometry");
@@ -938,93 +707,64 @@ at::Tensor conv_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t ks, int6
   TORCH_CHECK(g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo, "g must be (B, Ho, Wo, Cout) of this conv");
   const int64_t Kpad = (ks * ks * Cin + 31) / 32 * 32;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  float* fin = nullptr;
-  long long fs[4] = {0, 0, 0, 0};
-  int fco = 0, fci = 0;
-  if (out.has_value()) {
-    const at::Tensor& o = *out;
-    TORCH_CHECK(o.is_cuda() && o.scalar_type() == at::kFloat && o.dim() == 4 && o.device() == g.device(),
-                "out must be a float32 (Cout, Cin, ks, ks) tensor on the device");
-    TORCH_CHECK(o.size(0) <= Cout && o.size(1) <= Cin && o.size(2) == ks && o.size(3) == ks && o.size(0) > 0 &&
-                    o.size(1) > 0, "out must be (Cout_r <= Cout, Cin_r <= Cin, ks, ks)");
-    fin = o.data_ptr<float>();
-    fco = (int)o.size(0);
-    fci = (int)o.size(1);
-    for (int i = 0; i < 4; ++i) fs[i] = o.stride(i);
-  }
-  at::Tensor dw = fin ? at::Tensor() : at::empty({Cout, Kpad}, g.options());
-  const int64_t slices = (B * Ho * Wo + 31) / 32;
-  int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, slices));
-  const int64_t per = (slices + sp - 1) / sp;
-  sp = (slices + per - 1) / per;
-  at::Tensor ws;
-  if (sp > 1) ws = at::empty({sp * Cout * Kpad}, g.options());
-  TP_CHECK_HIP(tp_conv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), fin ? nullptr : dw.data_ptr<float>(),
-                             sp > 1 ? ws.data_ptr<float>() : nullptr, (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                             (int)ks, (int)stride, (int)pad, (int)Kpad, (int)cfg, (int)sp, fin, fco, fci,
-                             fin ? fs : nullptr, 1, 0, 0, cur_stream()));
-  return fin ? at::empty({0}, g.options()) : dw;  // with ``out`` the result is in ``out``
+  const ParamOut f = present(out) ? param_out(*out, Cout, Cin, ks, g) : ParamOut();
+  at::Tensor dw = f.p ? at::Tensor() : at::empty({Cout, Kpad}, g.options());
+  const int64_t sp = norm_splits(splits, (B * Ho * Wo + 31) / 32);
+  at::Tensor ws = splitk_ws(sp, Cout * Kpad, g);
+  TP_CHECK_HIP(tp_conv_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dw), ptr_or_null(ws), (int)B, (int)H,
+                             (int)W, (int)Cin, (int)Cout, (int)ks, (int)stride, (int)pad, (int)Kpad, (int)cfg, (int)sp,
+                             f.p, f.co, f.ci, f.p ? f.fs : nullptr, 1, 0, 0, cur_stream()));
+  return f.p ? at::empty({0}, g.options()) : dw;  // with ``out`` the result is in ``out``
 }
 
 // Training conv forward that also returns the BatchNorm statistics of its output: y (B, Ho, Wo,
 // Cout) and per M tile the column sums / sums of squares, (ceil(M / tile_m(cfg)), 2, Cout) fp64
 // (fold with bn_train_fwd(..., pre=)). No split-K, no epilogue besides the bias.
-std::tuple<at::Tensor, at::Tensor> conv_gen_stats(const at::Tensor& x, const at::Tensor& w,
-                                                  const c10::optional<at::Tensor>& shift, int64_t ks, int64_t stride,
-                                                  int64_t pad, int64_t cfg) {
-  need(x, "x", 4);
-  need(w, "w", 2);
-  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = w.size(0);
-  TORCH_CHECK((Cin % 4 == 0 && Cin >= 8 && (ks == 1 || ks == 3 || ks == 5)) ||
-                  (Cin == 4 && (ks == 3 || ks == 5 || ks == 7)),
-              "conv_gen_stats supports ks 1/3/5 with Cin % 4 == 0 (>= 8), or ks 3/5/7 with a 4-channel input");
-  TORCH_CHECK(w.size(1) == tp_conv_gen_k((int)ks, (int)Cin), "weight K mismatch");
-  TORCH_CHECK(stride >= 1 && pad >= 0 && Cout % 4 == 0, "bad geometry / Cout % 4");
-  const int64_t Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+std::tuple<at::Tensor, at::Tensor> conv_gen_stats(const at::Tensor& x, const at::Tensor& w, const OptTensor& shift,
+                                                  int64_t ks, int64_t stride, int64_t pad, int64_t cfg) {
+  const auto [B, H, W, Cin, Cout, Ho, Wo] = gen_shape(x, w, ks, stride, pad);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* sh = opt_ptr(shift, Cout, "shift");
+  const float* sh = opt_ptr(shift, Cout, "shift", x);
   auto out = at::empty({B, Ho, Wo, Cout}, x.options());
   const int64_t M = B * Ho * Wo, tm = tp_conv_tile_m((int)cfg);
   auto part = at::empty({(M + tm - 1) / tm, 2, Cout}, x.options().dtype(at::kDouble));
-  at::Tensor ws = Cin != 4 ? sk_workspace(cfg, ks, false, false, M, Cout, x.options()) : at::Tensor();
-  const int64_t cf = ws.defined() || cfg < 0 ? cfg : cfg & ~kCfgSK;
+  const SkPlan sk = sk_plan(Cin != 4, cfg, ks, false, M, Cout, x);
   TP_CHECK_HIP(tp_conv_gen(x.data_ptr<float>(), w.data_ptr<float>(), (int)B, (int)H, (int)W, (int)Cin, (int)Cout,
-                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)cf, 1, nullptr, sh, 0, nullptr, 1, nullptr,
-                           nullptr, out.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
-                           part.data_ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           cur_stream()));
+                           (int)ks, (int)stride, (int)pad, 0, 0, 0, (int)sk.cfg, 1, nullptr, sh, 0, nullptr, 1, nullptr,
+                           nullptr, out.data_ptr<float>(), ptr_or_null(sk.ws), part.data_ptr<double>(), nullptr, 0,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, cur_stream()));
   return {out, part};
 }
 
 // Winograd F(2x2,3x3) weight gradient of a stride-1 pad-1 3x3 conv: g (B, H, W, Cout), x (B, H, W,
-// Cin) NHWC (H, W even, Cin % 32 == 0) -> ``out`` (Cout_r, Cin_r, 3, 3), any strides (real channels).
+// Cin) NHWC (H, W even, Cin % 32 == 0) -> ``out`` (Cout_r, Cin_r, 3, 3), any positive strides (real channels).
 void wino_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t cfg, int64_t splits, at::Tensor& out) {
   need(g, "g", 4);
-  need(x, "x", 4);
+  need(x, "x", 4, &g);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = g.size(3);
   TORCH_CHECK(g.size(0) == B && g.size(1) == H && g.size(2) == W, "g must be (B, H, W, Cout) of a same-size conv");
   TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && Cin % 4 == 0 && Cin >= 8 && Cout % 4 == 0,
               "wino_wgrad needs even H/W, Cin % 4 (>= 8), Cout % 4");
-  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.dim() == 4 && out.size(2) == 3 &&
-                  out.size(3) == 3 && out.size(0) <= Cout && out.size(1) <= Cin && out.device() == g.device(),
-              "out must be a float32 (Cout_r, Cin_r, 3, 3) tensor on the device");
+  const ParamOut f = param_out(out, Cout, Cin, 3, g);
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
-  const int64_t T = B * (H / 2) * (W / 2);
-  const int64_t slices = (T + 31) / 32;
-  int64_t sp = std::max<int64_t>(1, std::min<int64_t>(splits, slices));
-  const int64_t per = (slices + sp - 1) / sp;
-  sp = (slices + per - 1) / per;
+  const int64_t sp = norm_splits(splits, (B * (H / 2) * (W / 2) + 31) / 32);
   auto ws = at::empty({tp_wino_wgrad_ws_elems((int)B, (int)H, (int)W, (int)Cin, (int)Cout, (int)sp)}, g.options());
-  long long fs[4];
-  for (int i = 0; i < 4; ++i) fs[i] = out.stride(i);
   TP_CHECK_HIP(tp_wino_wgrad(g.data_ptr<float>(), x.data_ptr<float>(), ws.data_ptr<float>(), (int)B, (int)H, (int)W,
-                             (int)Cin, (int)Cout, (int)cfg, (int)sp, out.data_ptr<float>(), (int)out.size(0),
-                             (int)out.size(1), fs, cur_stream()));
+                             (int)Cin, (int)Cout, (int)cfg, (int)sp, f.p, f.co, f.ci, f.fs, cur_stream()));
 }
 
-// Training-mode BatchNorm over the last dim of an NHWC activation x (..., C), C % 4 == 0.
+// (G, 2, C) fp64 statistics that the producing conv reduced per M tile (conv_gen_stats, conv_gen_bwd_bn); nullable
+const double* tile_stats(const OptTensor& pre, int64_t C, const at::Tensor& like) {
+  if (!present(pre)) return nullptr;
+  TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kDouble && pre->is_contiguous() && pre->dim() == 3 &&
+                  pre->size(0) > 0 && pre->size(1) == 2 && pre->size(2) == C && pre->device() == like.device(),
+              "pre must be (G, 2, C) float64 tile statistics on the device");
+  return pre->data_ptr<double>();
+}
+
+// Training-mode BatchNorm over the last dim of a channels-last activation x (..., C).
 // Updates running_mean / running_var in place (momentum, unbiased variance) when given.
-// Training BN on (.., C) channels-last data; optional fused residual add and ReLU:
+// Optional fused residual add and ReLU:
 // y = relu?(BN(x) + res?). Returns (y, mean, invstd).
 // With ``relu`` also returns the ReLU bit mask (ceil(P*C/4) bytes; else an empty tensor) for bn_train_bwd.
 // Any C (C % 4 == 0: float4 rows; else per-element). ``cr`` (0 = C): the channels with parameters /
@@ -1032,41 +772,27 @@ void wino_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t cfg, int64_t s
 // ``act``: the activation code, 0 none, 1 ReLU, 2 ReLU6 (y = min(max(v, 0), 6)); it wins over ``relu``
 // when non-zero, ``relu`` alone means 1. With an activation the bit mask is always returned (bit =
 // the gradient passes: v > 0, or 0 < v < 6 for ReLU6, whose backward has no other masking mode).
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
-                                                             const c10::optional<at::Tensor>& beta,
-                                                             const c10::optional<at::Tensor>& running_mean,
-                                                             const c10::optional<at::Tensor>& running_var, double eps,
-                                                             double momentum, const c10::optional<at::Tensor>& res,
-                                                             bool relu, const c10::optional<at::Tensor>& pre,
-                                                             const c10::optional<at::Tensor>& num_batches,
-                                                             int64_t cr, int64_t act_) {
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(
+    const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta, const OptTensor& running_mean,
+    const OptTensor& running_var, double eps, double momentum, const OptTensor& res, bool relu, const OptTensor& pre,
+    const OptTensor& num_batches, int64_t cr, int64_t act_) {
   TORCH_CHECK(act_ >= 0 && act_ <= 2, "act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got ", act_);
   const int act = act_ != 0 ? (int)act_ : (relu ? 1 : 0);
-  need(x, "x", -1);
+  need(x, "x", kAnyDims);
   const int64_t C = x.size(-1), P = x.numel() / std::max<int64_t>(C, 1);
   TORCH_CHECK(C > 0 && P > 0, "bn_train_fwd needs a non-empty batch");
   const int64_t Cr = cr > 0 ? cr : C;
   TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* ga = opt_ptr(gamma, Cr, "gamma");
-  const float* be = opt_ptr(beta, Cr, "beta");
-  float* rm = nullptr;
-  float* rv = nullptr;
-  if (running_mean.has_value() && running_mean->defined()) {
-    need(*running_mean, "running_mean", 1);
-    need(*running_var, "running_var", 1);
-    TORCH_CHECK(running_mean->numel() == Cr && running_var->numel() == Cr, "running stats must have cr elements");
-    rm = running_mean->data_ptr<float>();
-    rv = running_var->data_ptr<float>();
-  }
-  const float* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    need(*res, "res", -1);
-    TORCH_CHECK(res->sizes() == x.sizes(), "res must have x's shape");
-    rp = res->data_ptr<float>();
-  }
+  const float* ga = opt_ptr(gamma, Cr, "gamma", x);
+  const float* be = opt_ptr(beta, Cr, "beta", x);
+  // the running statistics are updated as a pair (a running_var alone is left untouched)
+  float* rm = vec_ptr(running_mean, Cr, "running_mean", x);
+  float* rv = rm ? vec_ptr(running_var, Cr, "running_var", x) : nullptr;
+  TORCH_CHECK(!rm || rv, "running_mean needs running_var");
+  const float* rp = same_shape_ptr(res, "res", x);
   long long* nbt = nullptr;  // the module's num_batches_tracked, incremented by the finalize kernel
-  if (num_batches.has_value() && num_batches->defined()) {
+  if (present(num_batches)) {
     TORCH_CHECK(num_batches->is_cuda() && num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 &&
                     num_batches->device() == x.device(), "num_batches must be a one-element int64 GPU tensor");
     nbt = reinterpret_cast<long long*>(num_batches->data_ptr<int64_t>());
@@ -1076,16 +802,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
   const int64_t Cs = (C + 3) / 4 * 4;  // row stride: every row 16-byte aligned (float4 reads) for any C
   auto stats = at::empty({4, Cs}, x.options()).narrow(1, 0, C);  // mean, invstd, a, b
   float* sp = stats.data_ptr<float>();
-  if (pre.has_value() && pre->defined()) {  // statistics reduced per tile by the producing conv
-    TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kDouble && pre->is_contiguous() && pre->dim() == 3 &&
-                    pre->size(1) == 2 && pre->size(2) == C && pre->device() == x.device(),
-                "pre must be conv_gen_stats' (G, 2, C) fp64 tile statistics");
+  if (const double* pp = tile_stats(pre, C, x)) {  // statistics reduced per tile by the producing conv
     const int64_t G = pre->size(0);
     auto ws = at::empty({2 * std::min<int64_t>(G, 256) * C}, x.options().dtype(at::kDouble));
-    TP_CHECK_HIP(tp_bn_fwd_train_pre(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
-                                    (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(),
-                                    pre->data_ptr<double>(), (int)G, rp, act,
-                                    act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
+    TP_CHECK_HIP(tp_bn_fwd_train_pre(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be,
+                                     (float)eps, (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs,
+                                     ws.data_ptr<double>(), pp, (int)G, rp, act,
+                                     act ? mk.data_ptr<uint8_t>() : nullptr, nbt, cur_stream()));
     return {y, stats[0], stats[1], mk};
   }
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
@@ -1100,61 +823,45 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(const at
 // also return that masked gradient (the residual branch's gradient). ``act``: the forward's
 // activation code; a ReLU6 forward (2) is masked by its bit mask only ("y > 0" is wrong for it).
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
-    const at::Tensor& g, const at::Tensor& x, const c10::optional<at::Tensor>& gamma, const at::Tensor& mean,
-    const at::Tensor& invstd, bool want_dx, const c10::optional<at::Tensor>& ym, bool want_dres,
-    const c10::optional<at::Tensor>& mask, int64_t cr, const c10::optional<at::Tensor>& pre, int64_t act) {
+    const at::Tensor& g, const at::Tensor& x, const OptTensor& gamma, const at::Tensor& mean,
+    const at::Tensor& invstd, bool want_dx, const OptTensor& ym, bool want_dres, const OptTensor& mask, int64_t cr,
+    const OptTensor& pre, int64_t act) {
+  const bool has_mask = present(mask) && mask->numel() > 0;  // (bn_train_fwd's mask is empty without an activation)
   TORCH_CHECK(act >= 0 && act <= 2, "act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got ", act);
-  TORCH_CHECK(act != 2 || ((!ym.has_value() || !ym->defined()) && mask.has_value() && mask->defined() &&
-                           mask->numel() > 0),
+  TORCH_CHECK(act != 2 || (!present(ym) && has_mask),
               "the backward of a ReLU6 forward takes bn_train_fwd's bit mask, not ym");
-  need(g, "g", -1);
-  need(x, "x", -1);
+  need(g, "g", kAnyDims);
+  need(x, "x", kAnyDims, &g);
   TORCH_CHECK(g.sizes() == x.sizes(), "g and x must have the same shape");
   const int64_t C = x.size(-1), P = x.numel() / std::max<int64_t>(C, 1);
   TORCH_CHECK(C > 0 && P > 0, "bn_train_bwd needs a non-empty batch");
   const int64_t Cr = cr > 0 ? cr : C;
   TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  const float* ga = opt_ptr(gamma, Cr, "gamma");
-  const float* mp = opt_ptr(mean, C, "mean");
-  const float* ip = opt_ptr(invstd, C, "invstd");
-  const float* yp = nullptr;
-  if (ym.has_value() && ym->defined()) {
-    need(*ym, "ym", -1);
-    TORCH_CHECK(ym->sizes() == x.sizes(), "ym must have x's shape");
-    yp = ym->data_ptr<float>();
-  }
-  const uint8_t* mkp = nullptr;
-  if (mask.has_value() && mask->defined() && mask->numel() > 0) {
-    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
-                    mask->numel() == (P * C + 3) / 4 && mask->device() == x.device(),
-                "mask must be bn_train_fwd's ReLU bit mask (ceil(P*C/4) uint8)");
-    mkp = mask->data_ptr<uint8_t>();
-  }
+  const float* ga = opt_ptr(gamma, Cr, "gamma", x);
+  const float* mp = opt_ptr(mean, C, "mean", x);
+  const float* ip = opt_ptr(invstd, C, "invstd", x);
+  const float* yp = same_shape_ptr(ym, "ym", x);
+  const uint8_t* mkp = has_mask ? bit_mask_ptr(mask, P * C, x, "mask") : nullptr;
   const int64_t Cs = (C + 3) / 4 * 4;
   auto coef = at::empty({5, Cs}, x.options());  // dgamma, dbeta, a, k1, k2 (16-byte aligned rows)
   at::Tensor dx, dres;
   if (want_dx) dx = at::empty_like(x);
   if (want_dres) dres = at::empty_like(x);
   float* cp = coef.data_ptr<float>();
-  if (pre.has_value() && pre->defined()) {  // statistics from the producing GEMM's epilogue (conv_gen_bwd_bn)
-    TORCH_CHECK(pre->is_cuda() && pre->scalar_type() == at::kDouble && pre->is_contiguous() && pre->dim() == 3 &&
-                    pre->size(1) == 2 && pre->size(2) == C && pre->size(0) > 0 && pre->device() == x.device(),
-                "pre must be (G, 2, C) float64 tile statistics");
+  if (const double* pp = tile_stats(pre, C, x)) {  // statistics from the producing GEMM's epilogue (conv_gen_bwd_bn)
     const int64_t G = pre->size(0);
     auto wsp = at::empty({2 * std::min<int64_t>(G, 256) * C}, x.options().dtype(at::kDouble));
-    TP_CHECK_HIP(tp_bn_bwd_train_pre(g.data_ptr<float>(), x.data_ptr<float>(),
-                                     want_dx ? dx.data_ptr<float>() : nullptr, (int)P, (int)C, (int)Cr, ga, mp, ip, cp,
-                                     cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs, wsp.data_ptr<double>(),
-                                     pre->data_ptr<double>(), (int)G, mkp ? nullptr : yp,
-                                     want_dres ? dres.data_ptr<float>() : nullptr, mkp, cur_stream()));
+    TP_CHECK_HIP(tp_bn_bwd_train_pre(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dx), (int)P, (int)C, (int)Cr,
+                                     ga, mp, ip, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
+                                     wsp.data_ptr<double>(), pp, (int)G, mkp ? nullptr : yp, ptr_or_null(dres), mkp,
+                                     cur_stream()));
     return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
   }
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
-  TP_CHECK_HIP(tp_bn_bwd_train(g.data_ptr<float>(), x.data_ptr<float>(), want_dx ? dx.data_ptr<float>() : nullptr,
-                               (int)P, (int)C, (int)Cr, ga, mp, ip, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
-                               ws.data_ptr<double>(), mkp ? nullptr : yp, want_dres ? dres.data_ptr<float>() : nullptr,
-                               mkp, cur_stream()));
+  TP_CHECK_HIP(tp_bn_bwd_train(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dx), (int)P, (int)C, (int)Cr, ga,
+                               mp, ip, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs, ws.data_ptr<double>(),
+                               mkp ? nullptr : yp, ptr_or_null(dres), mkp, cur_stream()));
   return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
 }
 

@@ -5,10 +5,11 @@ Design
 * Every ``csrc/kernels/*.hip`` file is plain HIP (no torch headers) and is compiled
   with ``hipcc --offload-arch=gfx950`` into an object file. Kernel files export
   host-side launcher functions that take raw device pointers + a ``hipStream_t``.
-* ``csrc/bindings.cpp`` is the only translation unit that includes torch. It
-  validates tensors (device / dtype / contiguity / shape — ops fail loudly on a
-  mismatch) and registers the ``torch.ops.tpamd.*`` operators with
-  ``TORCH_LIBRARY``.
+* ``csrc/bindings.cpp`` and ``csrc/engine_bindings.cpp`` are the two translation
+  units that include torch. They validate tensors (device / dtype / contiguity /
+  shape — ops fail loudly on a mismatch) with the checks of
+  ``csrc/include/tp_bind.h``, which both include and no kernel file does, and
+  register the ``torch.ops.tpamd.*`` operators with ``TORCH_LIBRARY``.
 * Everything is linked with ``-shared`` into ``torchpruner_amd/_C.so`` against the
   HIP runtime that ships inside torch (same soname ``libamdhip64.so.7``), so the
   extension shares torch's streams and caching allocator.
