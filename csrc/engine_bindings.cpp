@@ -791,12 +791,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(
   float* rv = rm ? vec_ptr(running_var, Cr, "running_var", x) : nullptr;
   TORCH_CHECK(!rm || rv, "running_mean needs running_var");
   const float* rp = same_shape_ptr(res, "res", x);
-  long long* nbt = nullptr;  // the module's num_batches_tracked, incremented by the finalize kernel
-  if (present(num_batches)) {
-    TORCH_CHECK(num_batches->is_cuda() && num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 &&
-                    num_batches->device() == x.device(), "num_batches must be a one-element int64 GPU tensor");
-    nbt = reinterpret_cast<long long*>(num_batches->data_ptr<int64_t>());
-  }
+  long long* nbt = counter_ptr(num_batches, x);  // the module's num_batches_tracked
   auto y = at::empty_like(x);
   auto mk = at::empty({act ? (P * C + 3) / 4 : 0}, x.options().dtype(at::kByte));
   const int64_t Cs = (C + 3) / 4 * 4;  // row stride: every row 16-byte aligned (float4 reads) for any C
@@ -865,6 +860,67 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
   return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
 }
 
+// y = hardswish(BN(x)), training mode, over the last dim of x (..., C): the statistics, running-stat and
+// ``cr`` semantics of bn_train_fwd, no residual and no mask. Returns (y, mean, invstd, ab) with ab (2, C)
+// the folded affine rows a = gamma * invstd, b = beta - mean * a that bn_hswish_bwd recomputes the
+// pre-activation from.
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_hswish_fwd(
+    const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta, const OptTensor& running_mean,
+    const OptTensor& running_var, double eps, double momentum, const OptTensor& num_batches, int64_t cr) {
+  need(x, "x", kAnyDims);
+  const int64_t C = x.dim() > 0 ? x.size(-1) : 0, P = x.numel() / std::max<int64_t>(C, 1);
+  TORCH_CHECK(C > 0 && P > 0, "bn_hswish_fwd needs a non-empty batch");
+  TORCH_CHECK(x.numel() < (1ll << 32), "bn_hswish_fwd: 2^32 elements or more");
+  const int64_t Cr = cr > 0 ? cr : C;
+  TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const float* ga = opt_ptr(gamma, Cr, "gamma", x);
+  const float* be = opt_ptr(beta, Cr, "beta", x);
+  float* rm = vec_ptr(running_mean, Cr, "running_mean", x);
+  float* rv = rm ? vec_ptr(running_var, Cr, "running_var", x) : nullptr;
+  TORCH_CHECK(!rm || rv, "running_mean needs running_var");
+  long long* nbt = counter_ptr(num_batches, x);
+  auto y = at::empty_like(x);
+  const int64_t Cs = (C + 3) / 4 * 4;  // row stride: every row 16-byte aligned (float4 reads) for any C
+  auto stats = at::empty({4, Cs}, x.options()).narrow(1, 0, C);  // mean, invstd, a, b
+  float* sp = stats.data_ptr<float>();
+  auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
+  TP_CHECK_HIP(tp_bn_hswish_fwd_train(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be,
+                                      (float)eps, (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs,
+                                      ws.data_ptr<double>(), nbt, cur_stream()));
+  return {y, stats[0], stats[1], stats.narrow(0, 2, 2)};
+}
+
+// Backward of bn_hswish_fwd: (dx or undefined, dgamma, dbeta). ``ab``: the forward's fourth output.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_hswish_bwd(const at::Tensor& g, const at::Tensor& x,
+                                                             const OptTensor& gamma, const at::Tensor& mean,
+                                                             const at::Tensor& invstd, const at::Tensor& ab,
+                                                             bool want_dx, int64_t cr) {
+  need(g, "g", kAnyDims);
+  need(x, "x", kAnyDims, &g);
+  TORCH_CHECK(g.sizes() == x.sizes(), "g and x must have the same shape");
+  const int64_t C = x.dim() > 0 ? x.size(-1) : 0, P = x.numel() / std::max<int64_t>(C, 1);
+  TORCH_CHECK(C > 0 && P > 0, "bn_hswish_bwd needs a non-empty batch");
+  TORCH_CHECK(x.numel() < (1ll << 32), "bn_hswish_bwd: 2^32 elements or more");
+  const int64_t Cr = cr > 0 ? cr : C;
+  TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const float* ga = opt_ptr(gamma, Cr, "gamma", x);
+  const float* mp = opt_ptr(mean, C, "mean", x);
+  const float* ip = opt_ptr(invstd, C, "invstd", x);
+  const auto [af, bf] = affine_rows(ab, C, x);
+  const int64_t Cs = (C + 3) / 4 * 4;
+  auto coef = at::empty({5, Cs}, x.options());  // dgamma, dbeta, a, k1, k2 (16-byte aligned rows)
+  at::Tensor dx;
+  if (want_dx) dx = at::empty_like(x);
+  float* cp = coef.data_ptr<float>();
+  auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
+  TP_CHECK_HIP(tp_bn_hswish_bwd_train(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dx), (int)P, (int)C,
+                                      (int)Cr, ga, mp, ip, af, bf, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
+                                      ws.data_ptr<double>(), cur_stream()));
+  return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr)};
+}
+
 void register_engine_ops_def(torch::Library& m) {
   m.def("wino_taylor_slots(int H, int W) -> int", &wino_taylor_slots);
   m.def("wino_lds_bytes() -> int", []() -> int64_t { return tp_wino_lds_bytes(); });
@@ -887,6 +943,11 @@ void register_engine_ops_def(torch::Library& m) {
   m.def("bn_train_bwd(Tensor g, Tensor x, Tensor? gamma, Tensor mean, Tensor invstd, bool want_dx, Tensor? ym=None, "
         "bool want_dres=False, Tensor? mask=None, int cr=0, Tensor? pre=None, int act=0) "
         "-> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("bn_hswish_fwd(Tensor x, Tensor? gamma, Tensor? beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
+        "float eps, float momentum, Tensor(c!)? num_batches=None, int cr=0) "
+        "-> (Tensor y, Tensor mean, Tensor invstd, Tensor ab)");
+  m.def("bn_hswish_bwd(Tensor g, Tensor x, Tensor? gamma, Tensor mean, Tensor invstd, Tensor ab, bool want_dx, "
+        "int cr=0) -> (Tensor dx, Tensor dgamma, Tensor dbeta)");
   m.def("conv_wgrad(Tensor g, Tensor x, int ks, int stride, int pad, int cfg, int splits, Tensor(a!)? out=None) "
         "-> Tensor");
   m.def("pack_conv_weight(Tensor w, int rows, int cols, int cpad, int mode) -> Tensor");
@@ -949,6 +1010,8 @@ void register_engine_ops_impl(torch::Library& m) {
   m.impl("wino_wgrad", &wino_wgrad);
   m.impl("bn_train_fwd", &bn_train_fwd);
   m.impl("bn_train_bwd", &bn_train_bwd);
+  m.impl("bn_hswish_fwd", &bn_hswish_fwd);
+  m.impl("bn_hswish_bwd", &bn_hswish_bwd);
   m.impl("unpool2_nhwc", &unpool2_nhwc);
   m.impl("conv_wino_dgrad", &conv_wino_dgrad);
   m.impl("wino4_weights", &wino4_weights);

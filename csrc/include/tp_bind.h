@@ -138,6 +138,26 @@ inline const uint8_t* bit_mask_ptr(const OptTensor& t, int64_t elems, const at::
   return t->data_ptr<uint8_t>();
 }
 
+// A BatchNorm module's num_batches_tracked, incremented by the finalize kernel (nullable).
+inline long long* counter_ptr(const OptTensor& t, const at::Tensor& like) {
+  if (!present(t)) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->numel() == 1 && t->device() == like.device(),
+              "num_batches must be a one-element int64 GPU tensor");
+  return reinterpret_cast<long long*>(t->data_ptr<int64_t>());
+}
+
+// The (2, C) rows a, b of a fused BN forward (unit stride along C; float4 reads when C % 4 == 0).
+inline std::tuple<const float*, const float*> affine_rows(const at::Tensor& ab, int64_t C, const at::Tensor& like) {
+  need(ab, "ab", kAnyLayout, &like);
+  TORCH_CHECK(ab.dim() == 2 && ab.size(0) == 2 && ab.size(1) == C, "ab must be (2, ", C, "), got ", ab.sizes());
+  TORCH_CHECK(ab.stride(1) == 1 && ab.stride(0) >= C, "ab: rows of unit stride");
+  const float* a = ab.data_ptr<float>();
+  const float* b = a + ab.stride(0);
+  TORCH_CHECK(C % 4 != 0 || (reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0),
+              "ab rows must be 16-byte aligned");
+  return {a, b};
+}
+
 // Output (B, H, W, K) of a forward conv on x, or with ``pool`` the 2x2-pooled output + its argmax bytes.
 inline std::tuple<at::Tensor, at::Tensor> conv_out(const at::Tensor& x, int64_t B, int64_t H, int64_t W, int64_t K,
                                                    bool pool) {

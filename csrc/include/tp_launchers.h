@@ -24,6 +24,15 @@ hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float* dx, int P,
                                const float* mean, const float* invstd, float* dgamma, float* dbeta, float* a,
                                float* k1, float* k2, double* ws, const double* pre, int G, const float* ym,
                                float* dres, const uint8_t* mk, hipStream_t st);
+// y = hardswish(BN(x)) and its backward (af / bf: the forward's a / b; no mask, no residual)
+hipError_t tp_bn_hswish_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                  const float* beta, float eps, float momentum, float* run_mean, float* run_var,
+                                  float* mean, float* invstd, float* a, float* b, double* ws, long long* nbt,
+                                  hipStream_t st);
+hipError_t tp_bn_hswish_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr, const float* gamma,
+                                  const float* mean, const float* invstd, const float* af, const float* bf,
+                                  float* dgamma, float* dbeta, float* a, float* k1, float* k2, double* ws,
+                                  hipStream_t st);
 // channel_reduce.hip
 hipError_t tp_channel_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C, int S,
                              int mode, int channels_last, hipStream_t st);

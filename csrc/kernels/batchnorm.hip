@@ -396,6 +396,151 @@ __global__ __launch_bounds__(256) void bn_fold_tiles(const double* __restrict__ 
   }
 }
 
+// ---- BN + Hardswish (MobileNetV3 units): y = hswish(v), v = x * a[c] + b[c] -------------------------
+// No mask and no saved v: the backward recomputes v from x and the forward's (a, b) through the same
+// bn_pre(), so both passes see the same v bit for bit (one explicit fma, whatever the contraction
+// mode). hswish is ATen's expression, evaluated in its order (a NaN v gives NaN: max(NaN + 3, 0) = 0,
+// NaN * 0 = NaN); hswish_bwd has the branch order of ATen's hardswish_backward (a NaN v passes g).
+// A padding channel (a = b = 0) gives v = 0 and y = 0.
+__device__ __forceinline__ float bn_pre(float x, float a, float b) { return fmaf(x, a, b); }
+__device__ __forceinline__ float hswish(float v) { return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
+__device__ __forceinline__ float hswish_bwd(float g, float v) {
+  if (v < -3.f) return 0.f;
+  if (v <= 3.f) return g * (v / 3.f + 0.5f);
+  return g;
+}
+__device__ __forceinline__ float4 hswish_bwd4(float4 g, float4 x, float4 a, float4 b) {
+  return make_float4(hswish_bwd(g.x, bn_pre(x.x, a.x, b.x)), hswish_bwd(g.y, bn_pre(x.y, a.y, b.y)),
+                     hswish_bwd(g.z, bn_pre(x.z, a.z, b.z)), hswish_bwd(g.w, bn_pre(x.w, a.w, b.w)));
+}
+
+// Backward statistics (sum gm, sum gm * xhat) with gm = g * hswish'(x * af + bf), per row group into
+// the [groups][2][C] workspace of bn_partial<1> (same block shape, same row walk, same fold order).
+template <bool V4>
+__global__ __launch_bounds__(BN_T) void bn_hswish_partial(const float* __restrict__ x, const float* __restrict__ g,
+                                                          const float* __restrict__ mean,
+                                                          const float* __restrict__ invstd,
+                                                          const float* __restrict__ af, const float* __restrict__ bf,
+                                                          double* __restrict__ part, int P, int C,
+                                                          int rows_per_group) {
+  __shared__ double red[2][BN_RL][BN_CQ * 4];
+  const int cq = threadIdx.x % BN_CQ, rl = threadIdx.x / BN_CQ;
+  const int c = (blockIdx.x * BN_CQ + cq) * 4;
+  const int r0 = blockIdx.y * rows_per_group, r1 = min(P, r0 + rows_per_group);
+  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+  if (c < C) {
+    const float4 mu = ld4<V4>(mean, 0, c, C), is = ld4<V4>(invstd, 0, c, C);
+    const float4 av = ld4<V4>(af, 0, c, C), bv = ld4<V4>(bf, 0, c, C);
+    constexpr int U = 4;  // 8 loads in flight per thread
+    int r = r0 + rl;
+    for (; r + (U - 1) * BN_RL < r1; r += U * BN_RL) {
+      float4 v[U], d[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        v[u] = ld4<V4>(x, (size_t)(r + u * BN_RL) * C, c, C);
+        d[u] = ld4<V4>(g, (size_t)(r + u * BN_RL) * C, c, C);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float4 m = hswish_bwd4(d[u], v[u], av, bv);
+        s0.x += m.x;
+        s0.y += m.y;
+        s0.z += m.z;
+        s0.w += m.w;
+        s1.x += m.x * (v[u].x - mu.x) * is.x;
+        s1.y += m.y * (v[u].y - mu.y) * is.y;
+        s1.z += m.z * (v[u].z - mu.z) * is.z;
+        s1.w += m.w * (v[u].w - mu.w) * is.w;
+      }
+    }
+    for (; r < r1; r += BN_RL) {
+      const float4 v = ld4<V4>(x, (size_t)r * C, c, C);
+      const float4 m = hswish_bwd4(ld4<V4>(g, (size_t)r * C, c, C), v, av, bv);
+      s0.x += m.x;
+      s0.y += m.y;
+      s0.z += m.z;
+      s0.w += m.w;
+      s1.x += m.x * (v.x - mu.x) * is.x;
+      s1.y += m.y * (v.y - mu.y) * is.y;
+      s1.z += m.z * (v.z - mu.z) * is.z;
+      s1.w += m.w * (v.w - mu.w) * is.w;
+    }
+  }
+  red[0][rl][cq * 4 + 0] = s0.x;
+  red[0][rl][cq * 4 + 1] = s0.y;
+  red[0][rl][cq * 4 + 2] = s0.z;
+  red[0][rl][cq * 4 + 3] = s0.w;
+  red[1][rl][cq * 4 + 0] = s1.x;
+  red[1][rl][cq * 4 + 1] = s1.y;
+  red[1][rl][cq * 4 + 2] = s1.z;
+  red[1][rl][cq * 4 + 3] = s1.w;
+  __syncthreads();
+  if (threadIdx.x < 2 * BN_CQ * 4) {
+    const int which = threadIdx.x / (BN_CQ * 4), col = threadIdx.x % (BN_CQ * 4);
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < BN_RL; ++i) t += red[which][i][col];
+    const int cc = blockIdx.x * BN_CQ * 4 + col;
+    if (cc < C) part[((size_t)blockIdx.y * 2 + which) * C + cc] = t;
+  }
+}
+
+// forward (BWD = false): out = hswish(x * a + b)
+// backward (BWD = true): out = gm * a + k1 + k2 * x, gm = g * hswish'(x * af + bf); channels c >= Cr
+// (padding) get an exact 0 whatever g holds there
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_hswish_apply(const float* __restrict__ x, const float* __restrict__ g,
+                                                       const float* __restrict__ af, const float* __restrict__ bf,
+                                                       const float* __restrict__ a, const float* __restrict__ k1,
+                                                       const float* __restrict__ k2, float* __restrict__ out,
+                                                       unsigned n4, unsigned C4, unsigned Cr) {
+  for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
+    const unsigned c = (t % C4) * 4;
+    const float4 v = reinterpret_cast<const float4*>(x)[t];
+    const float4 fa = *reinterpret_cast<const float4*>(af + c);
+    const float4 fb = *reinterpret_cast<const float4*>(bf + c);
+    float4 o;
+    if (BWD) {
+      const float4 m = hswish_bwd4(reinterpret_cast<const float4*>(g)[t], v, fa, fb);
+      const float4 av = *reinterpret_cast<const float4*>(a + c);
+      const float4 bv = *reinterpret_cast<const float4*>(k1 + c);
+      const float4 kv = *reinterpret_cast<const float4*>(k2 + c);
+      o.x = c + 0 < Cr ? m.x * av.x + bv.x + kv.x * v.x : 0.f;
+      o.y = c + 1 < Cr ? m.y * av.y + bv.y + kv.y * v.y : 0.f;
+      o.z = c + 2 < Cr ? m.z * av.z + bv.z + kv.z * v.z : 0.f;
+      o.w = c + 3 < Cr ? m.w * av.w + bv.w + kv.w * v.w : 0.f;
+    } else {
+      o.x = hswish(bn_pre(v.x, fa.x, fb.x));
+      o.y = hswish(bn_pre(v.y, fa.y, fb.y));
+      o.z = hswish(bn_pre(v.z, fa.z, fb.z));
+      o.w = hswish(bn_pre(v.w, fa.w, fb.w));
+    }
+    reinterpret_cast<float4*>(out)[t] = o;
+  }
+}
+
+// bn_hswish_apply for C % 4 != 0: thread t owns flat elements 4t..4t+3 (< n), each with its own
+// channel (e % C), per-element loads and stores
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_hswish_apply_any(const float* __restrict__ x, const float* __restrict__ g,
+                                                           const float* __restrict__ af, const float* __restrict__ bf,
+                                                           const float* __restrict__ a, const float* __restrict__ k1,
+                                                           const float* __restrict__ k2, float* __restrict__ out,
+                                                           unsigned long long n, unsigned C, unsigned Cr) {
+  const unsigned long long n4 = (n + 3) / 4;
+  for (unsigned long long t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += (unsigned long long)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned long long e = 4 * t + q;
+      if (e >= n) break;
+      const unsigned c = (unsigned)(e % C);
+      const float xv = x[e], v = bn_pre(xv, af[c], bf[c]);
+      if (BWD) out[e] = c < Cr ? hswish_bwd(g[e], v) * a[c] + k1[c] + k2[c] * xv : 0.f;
+      else out[e] = hswish(v);
+    }
+  }
+}
+
 inline int bn_groups(int P, int C) {
   const int col_blocks = (C + BN_CQ * 4 - 1) / (BN_CQ * 4);
   int groups = std::max(1, std::min(1024, 1024 / std::max(1, col_blocks)));
@@ -512,5 +657,64 @@ extern "C" hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float*
                                                       k2, bn_fold_lanes());
   if (dx || dres)
     apply_launch<true>(x, g, a, k1, k2, dx, P, C, nullptr, 0, ym, dres, const_cast<uint8_t*>(mk), st);
+  return hipGetLastError();
+}
+
+namespace tp {
+// launch bn_hswish_apply (float4 rows) or bn_hswish_apply_any (per-element) over the (P, C) activation
+template <bool BWD>
+static void hswish_apply_launch(const float* x, const float* g, const float* af, const float* bf, const float* a,
+                                const float* k1, const float* k2, float* out, long long P, int C, int Cr,
+                                hipStream_t st) {
+  const long long n = P * C;
+  if (C % 4 == 0) {
+    const unsigned n4 = (unsigned)(n / 4);
+    bn_hswish_apply<BWD><<<(unsigned)std::min<long long>(ceil_div((long long)n4, 256), 8192), 256, 0, st>>>(
+        x, g, af, bf, a, k1, k2, out, n4, (unsigned)(C / 4), (unsigned)Cr);
+  } else {
+    const long long n4 = (n + 3) / 4;
+    bn_hswish_apply_any<BWD><<<(unsigned)std::min<long long>(ceil_div(n4, 256), 8192), 256, 0, st>>>(
+        x, g, af, bf, a, k1, k2, out, (unsigned long long)n, (unsigned)C, (unsigned)Cr);
+  }
+}
+}  // namespace tp
+
+// Fused unit tail y = hardswish(BN(x)) (MobileNetV3's Conv-BN-Hardswish units): the statistics pass
+// and the finalize of tp_bn_fwd_train (same running statistics, nbt, mean / invstd / a / b), then one
+// apply pass. No residual, no mask: the backward recomputes the pre-activation from x and (a, b).
+extern "C" hipError_t tp_bn_hswish_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                             const float* beta, float eps, float momentum, float* run_mean,
+                                             float* run_var, float* mean, float* invstd, float* a, float* b,
+                                             double* ws, long long* nbt, hipStream_t st) {
+  using namespace tp;
+  if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
+  const int groups = bn_groups(P, C);
+  const int rpg = (P + groups - 1) / groups;
+  const dim3 grid((C + BN_CQ * 4 - 1) / (BN_CQ * 4), groups);
+  partial_launch<0>(grid, x, nullptr, nullptr, nullptr, ws, P, C, rpg, nullptr, nullptr, st);
+  bn_fwd_finalize<<<(C + 15) / 16, BN_FIN_T, 0, st>>>(ws, groups, P, C, Cr, gamma, beta, eps, momentum, run_mean,
+                                                    run_var, mean, invstd, a, b, nbt, bn_fold_lanes());
+  hswish_apply_launch<false>(x, nullptr, a, b, nullptr, nullptr, nullptr, y, P, C, Cr, st);
+  return hipGetLastError();
+}
+
+// Its backward. af / bf: the forward's a / b as it wrote them (the pre-activation is recomputed from
+// them, not from gamma / mean / invstd). dx nullable (dgamma / dbeta only). Channels c >= Cr: padding
+// (dx = 0 there, no dgamma / dbeta written). ws as tp_bn_bwd_train.
+extern "C" hipError_t tp_bn_hswish_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
+                                             const float* gamma, const float* mean, const float* invstd,
+                                             const float* af, const float* bf, float* dgamma, float* dbeta, float* a,
+                                             float* k1, float* k2, double* ws, hipStream_t st) {
+  using namespace tp;
+  if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
+  if (!af || !bf) return hipErrorInvalidValue;
+  const int groups = bn_groups(P, C);
+  const int rpg = (P + groups - 1) / groups;
+  const dim3 grid((C + BN_CQ * 4 - 1) / (BN_CQ * 4), groups);
+  if (C % 4 == 0) bn_hswish_partial<true><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+  else bn_hswish_partial<false><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+  bn_bwd_finalize<<<(C + 15) / 16, BN_FIN_T, 0, st>>>(ws, groups, P, C, Cr, gamma, mean, invstd, dgamma, dbeta, a, k1,
+                                                      k2, bn_fold_lanes());
+  if (dx) hswish_apply_launch<true>(x, g, af, bf, a, k1, k2, dx, P, C, Cr, st);
   return hipGetLastError();
 }

@@ -213,6 +213,7 @@ HOST_PROGRAMS = {
     "dwconv_act_validation": ("dwconv_act",),
     "dwconv_carried_validation": ("dwconv", "batchnorm"),
     "se_validation": ("squeeze_excite",),
+    "bn_hswish_validation": ("batchnorm",),
     "prefix_project_validation": ("prefix_project",),
     "conv2x2_fast_validation": ("conv_mfma", "conv2x2_fast"),
     "elementwise_validation": ("channel_reduce", "prune_ops", "shapley", "train_ops", "data_ops"),

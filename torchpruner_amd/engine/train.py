@@ -26,7 +26,11 @@ shortcut in its apply pass; ``TORCHPRUNER_FUSE_RELU6=0`` keeps the unfused path.
 Squeeze-and-excitation gates (MobileNetV3, EfficientNet: :class:`_NativeSE`) run as three passes over
 the expanded activation forward (pool, scale: two reads, one write) and four backward (one read of
 g and x for the product-reduce, one read of g and one write for ``dx``), with both FCs of the gate in
-one launch each way; Hardswish stays an ATen op.
+one launch each way. A ``(BatchNorm2d, Hardswish)`` pair of a plain ``nn.Sequential`` (the stem, the
+expand and depthwise units of the Hardswish blocks, the last conv) runs as one fused tail
+(:func:`bn_hswish`: statistics, then one apply pass; the backward recomputes the pre-activation from
+x and the forward's folded affine, nothing but x is kept); ``TORCHPRUNER_FUSE_HSWISH=0`` keeps the
+native BN followed by ATen's hardswish. The classifier's ``Linear -> Hardswish`` stays an ATen op.
 
 Training-mode ``BatchNorm2d`` runs on deterministic NHWC batch-statistics / normalisation /
 backward kernels (K5, ``tpamd.bn_train_*``), training-mode ``nn.Dropout`` on a counter-based
@@ -177,8 +181,12 @@ _BWD_FUSE = os.environ.get("TORCHPRUNER_BN_BWD_FUSE", "1") != "0"
 _MB_FUSE = os.environ.get("TORCHPRUNER_FUSE_RELU6", "1") != "0"
 # passes that took each fusion (tests / diagnostics). Backward: tail statistics from a dgrad epilogue,
 # identity gradients handed over unmasked. Forward: fused BN + ReLU6 tails, inverted-residual blocks
-# on the fused block forward, depthwise convs on a carried (padded) width
-FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0, "bn_relu6": 0, "ir_block": 0, "dw_carried": 0}
+# on the fused block forward, depthwise convs on a carried (padded) width, fused BN + Hardswish tails
+FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0, "bn_relu6": 0, "ir_block": 0, "dw_carried": 0,
+               "bn_hswish": 0}
+# TORCHPRUNER_FUSE_HSWISH=0: (BatchNorm2d, Hardswish) pairs of an nn.Sequential stay unfused (the native
+# BN, then ATen's hardswish on the real-width slice); A/B switch, consulted at every Sequential forward
+_HS_FUSE = os.environ.get("TORCHPRUNER_FUSE_HSWISH", "1") != "0"
 # TORCHPRUNER_NATIVE_DW=0: depthwise convs stay on the library path (A/B switch, read once)
 _NATIVE_DW = os.environ.get("TORCHPRUNER_NATIVE_DW", "1") != "0"
 # launches of the depthwise kernels (tests / diagnostics)
@@ -811,6 +819,54 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, res: torch.Tensor = None, relu: 
                               act == 1, pre, nbt, bn.num_features, link if act == 1 else None, act)
 
 
+class _NativeBNHswish(torch.autograd.Function):
+    """Fused training-mode unit tail ``hardswish(BN(x))`` (MobileNetV3): BN statistics, then one apply
+    pass that normalises and activates. Hardswish's backward needs the pre-activation's value, not a
+    mask bit; it is recomputed from x (which the BN backward reads anyway) and the forward's folded
+    affine rows ``ab``, so neither the pre-activation nor the output is saved, and ATen's hardswish /
+    hardswish_backward passes disappear."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, nbt=None, cr=0):
+        xh = _nhwc(x)
+        w = weight.detach() if weight is not None else None
+        b = bias.detach() if bias is not None else None
+        y, mean, invstd, ab = ops.require().bn_hswish_fwd(xh, w, b, running_mean, running_var, float(eps),
+                                                          float(momentum), nbt, int(cr))
+        FUSE_COUNTS["bn_hswish"] += 1
+        ctx.cr = int(cr)
+        if running_mean is not None:
+            epochs.bump_stats()  # running stats written by the kernel: no version bump
+        ctx.save_for_backward(xh, w if w is not None else torch.empty(0, device=x.device), mean, invstd, ab)
+        ctx.has_w, ctx.has_b = weight is not None, bias is not None
+        return _as_nchw(y)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xh, w, mean, invstd, ab = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.require().bn_hswish_bwd(_nhwc(gy), xh, w if ctx.has_w else None, mean, invstd, ab,
+                                                        ctx.needs_input_grad[0], ctx.cr)
+        return (_as_nchw(dx) if ctx.needs_input_grad[0] else None, dgamma if ctx.has_w else None,
+                dbeta if ctx.has_b else None, None, None, None, None, None, None)
+
+
+def bn_hswish(bn: nn.BatchNorm2d, x: torch.Tensor) -> torch.Tensor:
+    """``hardswish(bn(x))`` — fused on the native kernels in training mode (fp32 GPU input at the
+    module's width, or a padded activation carrying more: it stays padded, hardswish(0) = 0), the
+    module's own ops otherwise (eval mode, unsupported inputs)."""
+    if not _bn_fusable(bn, x):
+        return F.hardswish(bn(_real(x, bn.num_features)))
+    momentum, nbt = bn.momentum, _bn_counter(bn)
+    if nbt is None and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if momentum is None:
+            momentum = 1.0 / float(bn.num_batches_tracked)
+    rm = bn.running_mean if bn.track_running_stats else None
+    rv = bn.running_var if bn.track_running_stats else None
+    return _NativeBNHswish.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, momentum if momentum is not None else 0.0,
+                                 nbt, bn.num_features)
+
+
 def _block_kind(m) -> str | None:
     """torchvision-layout residual blocks whose training forward can use the fused tails."""
     names = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
@@ -888,7 +944,9 @@ def _sequential_forward(self, x, mb):
     conv (no slice / pad copies at pruned widths); any other module gets the real width.
     ``mb`` (the MobileNet fusions, :data:`_MB_FUSE` when the forward was installed): (BatchNorm2d,
     ReLU6) pairs fuse too, ReLU6 passes a padded activation on, and a native depthwise conv takes
-    the padded activation and keeps it padded."""
+    the padded activation and keeps it padded. With or without ``mb``, a (BatchNorm2d, Hardswish)
+    pair runs as one :func:`bn_hswish` tail and passes a padded activation on padded, unless
+    :data:`_HS_FUSE` is off (read here, at call time) or one of the two modules has a hook."""
     mods = list(self.children())
     real = None  # real channel count while x is a padded activation
     i = 0
@@ -897,6 +955,11 @@ def _sequential_forward(self, x, mb):
         if isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and _bn_fusable(m, x) \
                 and (isinstance(mods[i + 1], nn.ReLU) or (mb and type(mods[i + 1]) is nn.ReLU6)):
             x = bn_act(m, x, act=2 if type(mods[i + 1]) is nn.ReLU6 else 1)
+            i += 2
+            continue
+        if _HS_FUSE and isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and type(mods[i + 1]) is nn.Hardswish \
+                and _bn_fusable(m, x) and not _any_hooked((m, mods[i + 1])):
+            x = bn_hswish(m, x)  # a padded activation stays padded: hardswish(0) = 0
             i += 2
             continue
         if "forward" in m.__dict__ and getattr(m.forward, "__func__", None) is _native_forward \
@@ -1221,15 +1284,19 @@ def _ir_kind(m) -> str | None:
     return "expand" if len(units) == 2 else "dw"
 
 
-def _hooked(block) -> bool:
-    """Whether a module inside ``block`` has hooks, or global module hooks are registered: a fused
-    block forward does not call those modules, so it must not run then."""
+def _any_hooked(mods) -> bool:
+    """Whether one of ``mods`` has hooks, or global module hooks are registered: a fused forward does
+    not call the modules it replaces, so it must not run then."""
     mod = torch.nn.modules.module
     if mod._global_forward_hooks or mod._global_forward_pre_hooks or mod._global_backward_hooks \
             or mod._global_backward_pre_hooks:
         return True
-    return any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks
-               for m in block.modules() if m is not block)
+    return any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks for m in mods)
+
+
+def _hooked(block) -> bool:
+    """:func:`_any_hooked` over the modules inside ``block`` (a fused block forward calls none of them)."""
+    return _any_hooked(m for m in block.modules() if m is not block)
 
 
 class _Shape:
@@ -1367,7 +1434,11 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
     forward whenever one of them has a forward / backward hook or global module hooks exist (the
     inner Sequentials keep their own forwards for that). ``(BatchNorm2d, ReLU6)`` pairs of any
     other ``nn.Sequential`` fuse like ``(BatchNorm2d, ReLU)`` ones. ``TORCHPRUNER_FUSE_RELU6=0``
-    turns the ReLU6 fusions and the block forward off. Also switched: depthwise convs
+    turns the ReLU6 fusions and the block forward off. ``(BatchNorm2d, Hardswish)`` pairs of an
+    ``nn.Sequential`` (MobileNetV3 units) run as one fused tail in training mode (:func:`bn_hswish`;
+    neither module is called then), except when one of the two has a forward / backward hook or
+    global module hooks exist: the pair then runs its modules; ``TORCHPRUNER_FUSE_HSWISH=0`` turns
+    this fusion off. Also switched: depthwise convs
     (:func:`dw_eligible`, the NHWC stencil kernels; ``TORCHPRUNER_NATIVE_DW=0`` leaves them on the
     library path), squeeze-and-excitation gates (:func:`se_eligible`, train and eval mode, with or
     without ``fuse``: pool, both FCs, gate and scale on the ``squeeze_excite`` kernels; the modules

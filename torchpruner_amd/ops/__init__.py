@@ -11,6 +11,7 @@ from typing import Sequence
 import torch
 
 from ._native import available, backend, load, require, use_native
+from .bn_hswish import bn_hswish_bwd, bn_hswish_fwd
 from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 from .se import SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_bwd, se_gate_fwd, se_pool, se_scale, se_wgrad
 
@@ -20,6 +21,7 @@ __all__ = [
     "gather_multi", "prefix_mask", "prefix_project", "shapley_scatter", "shapley_column", "cross_entropy",
     "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
     "SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad",
+    "bn_hswish_fwd", "bn_hswish_bwd",
 ]
 
 REDUCE_MODES = {"taylor": 0, "taylor_signed": 1, "sensitivity": 2, "apoz": 3, "sum_grad": 4}
