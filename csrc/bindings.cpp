@@ -569,6 +569,92 @@ at::Tensor dwconv_act_dgrad(const at::Tensor& g, const at::Tensor& y, const at::
   return dz;
 }
 
+void check_dwhs_acts(int64_t in_act, int64_t out_act) {
+  TORCH_CHECK(in_act >= 0 && in_act <= 3 && out_act >= 0 && out_act <= 3,
+              "activation codes are 0 (none), 1 (ReLU), 2 (ReLU6), 3 (Hardswish), got ", in_act, " / ", out_act);
+}
+
+// dwconv_act_fwd with activation code 3 (Hardswish) on either side; pre (the shape of y) receives the
+// output's pre-activation, the y operand of dwconv_hs_dgrad when out_act == 3
+at::Tensor dwconv_hs_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
+                         int64_t s, int64_t pad, int64_t in_act, int64_t out_act,
+                         const c10::optional<at::Tensor>& apoz, const c10::optional<at::Tensor>& pre) {
+  need(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "x must be a non-empty contiguous NHWC tensor");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  check_dwa_params(w, scale, &shift, C, x);
+  check_dwhs_acts(in_act, out_act);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  TORCH_CHECK(x.numel() < (int64_t(1) << 29), "x exceeds the kernels' 2 GiB operand range");
+  const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+  float *ap = nullptr, *pp = nullptr;
+  if (present(apoz)) {
+    need(*apoz, "apoz", 2, &x);
+    TORCH_CHECK(apoz->size(0) == B && apoz->size(1) == C, "apoz must be a contiguous (B, C) tensor");
+    ap = apoz->data_ptr<float>();
+  }
+  if (present(pre)) {
+    need(*pre, "pre", 4, &x);
+    TORCH_CHECK(pre->size(0) == B && pre->size(1) == Ho && pre->size(2) == Wo && pre->size(3) == C,
+                "pre must be a contiguous (B, Ho, Wo, C) tensor");
+    pp = pre->data_ptr<float>();
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty({B, Ho, Wo, C}, x.options());
+  TP_CHECK_HIP(tp_dwconv_hs_fwd(x.data_ptr<float>(), w.data_ptr<float>(), scale.data_ptr<float>(),
+                                shift.data_ptr<float>(), y.data_ptr<float>(), ap, pp, (int)B, (int)H, (int)W, (int)C,
+                                (int)k, (int)s, (int)pad, (int)in_act, (int)out_act, cur_stream()));
+  return y;
+}
+
+int64_t dwconv_hs_tay_slots(int64_t H, int64_t W, int64_t C) {
+  TORCH_CHECK(H > 0 && W > 0 && C > 0 && H < (int64_t(1) << 29) && W < (int64_t(1) << 29) && C < (int64_t(1) << 29),
+              "bad shape");
+  return tp_dwconv_hs_tay_slots((int)H, (int)W, (int)C);
+}
+
+// dz = d_in(z) * dA, dA = dwconv^T(g * scale * d_out(y)): y is the stored output for out_act 1 / 2 and
+// the stored pre-activation for out_act 3; tay as dwconv_act_dgrad
+at::Tensor dwconv_hs_dgrad(const at::Tensor& g, const at::Tensor& y, const at::Tensor& w, const at::Tensor& scale,
+                           const at::Tensor& z, int64_t H, int64_t W, int64_t s, int64_t pad, int64_t in_act,
+                           int64_t out_act, const c10::optional<at::Tensor>& tay, int64_t tay_mode) {
+  need(g, "g");
+  need(y, "y");
+  need(z, "z");
+  TORCH_CHECK(z.dim() == 4 && z.is_contiguous() && z.numel() > 0 && z.size(1) == H && z.size(2) == W,
+              "z must be a non-empty contiguous (B, H, W, C) tensor");
+  const int64_t B = z.size(0), C = z.size(3);
+  check_dwa_params(w, scale, nullptr, C, z);
+  check_dwhs_acts(in_act, out_act);
+  const int64_t k = w.size(2);
+  check_dw_geometry(H, W, k, s, pad);
+  const int64_t Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+  TORCH_CHECK(g.dim() == 4 && g.is_contiguous() && g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo &&
+                  g.size(3) == C && g.device() == z.device(), "g must be a contiguous (B, Ho, Wo, C) tensor");
+  TORCH_CHECK(y.sizes() == g.sizes() && y.is_contiguous() && y.device() == z.device(), "y must match g");
+  TORCH_CHECK(z.numel() < (int64_t(1) << 29), "z exceeds the kernels' 2 GiB operand range");
+  float* tp = nullptr;
+  int R = 0;
+  if (present(tay)) {
+    need(*tay, "tay");
+    TORCH_CHECK(tay_mode == 0 || tay_mode == 1, "tay_mode is 0 (Taylor) or 1 (Sensitivity)");
+    R = tp_dwconv_hs_tay_slots((int)H, (int)W, (int)C);
+    TORCH_CHECK(tay->dim() == 3 && tay->size(0) == R && tay->size(1) == B && tay->size(2) == C &&
+                    tay->is_contiguous() && tay->device() == z.device(),
+                "tay must be a contiguous (dwconv_hs_tay_slots(H, W, C), B, C) slab");
+    TORCH_CHECK(tay->numel() < (int64_t(1) << 29), "tay exceeds the kernels' 2 GiB operand range");
+    tp = tay->data_ptr<float>();
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto dz = at::empty_like(z);
+  TP_CHECK_HIP(tp_dwconv_hs_dgrad(g.data_ptr<float>(), y.data_ptr<float>(), w.data_ptr<float>(),
+                                  scale.data_ptr<float>(), z.data_ptr<float>(), dz.data_ptr<float>(), tp, R,
+                                  (int)tay_mode, (int)B, (int)H, (int)W, (int)C, (int)k, (int)s, (int)pad,
+                                  (int)in_act, (int)out_act, cur_stream()));
+  return dz;
+}
+
 at::Tensor avgpool_bwd(const at::Tensor& g_, int64_t H, int64_t W) {
   need(g_, "g");
   auto g = g_.contiguous();
@@ -771,6 +857,11 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("dwconv_act_dgrad(Tensor g, Tensor y, Tensor w, Tensor scale, Tensor z, int H, int W, int stride, int pad, "
         "int in_act, int out_act, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
   m.def("dwconv_act_tay_slots(int H, int W, int C) -> int", &dwconv_act_tay_slots);
+  m.def("dwconv_hs_fwd(Tensor x, Tensor w, Tensor scale, Tensor shift, int stride, int pad, int in_act, int out_act, "
+        "Tensor(a!)? apoz=None, Tensor(b!)? pre=None) -> Tensor");
+  m.def("dwconv_hs_dgrad(Tensor g, Tensor y, Tensor w, Tensor scale, Tensor z, int H, int W, int stride, int pad, "
+        "int in_act, int out_act, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
+  m.def("dwconv_hs_tay_slots(int H, int W, int C) -> int", &dwconv_hs_tay_slots);
   register_engine_ops_def(m);
 }
 
@@ -796,6 +887,8 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("dwconv_wgrad", &dwconv_wgrad);
   m.impl("dwconv_act_fwd", &dwconv_act_fwd);
   m.impl("dwconv_act_dgrad", &dwconv_act_dgrad);
+  m.impl("dwconv_hs_fwd", &dwconv_hs_fwd);
+  m.impl("dwconv_hs_dgrad", &dwconv_hs_dgrad);
   m.impl("se_pool", &se_pool);
   m.impl("se_gate_fwd", &se_gate_fwd);
   m.impl("se_scale", &se_scale);

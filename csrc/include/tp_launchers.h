@@ -109,6 +109,15 @@ int tp_dwconv_act_tay_slots(int H, int W, int C);
 hipError_t tp_dwconv_act_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
                                float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
                                int pad, int in_act, int out_act, hipStream_t st);
+// the same with code 3 (Hardswish) on either side; pre (optional): the output's pre-activation, which is
+// the y operand of the dgrad when out_act == 3
+hipError_t tp_dwconv_hs_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
+                            float* apoz, float* pre, int B, int H, int W, int C, int k, int s, int pad, int in_act,
+                            int out_act, hipStream_t st);
+int tp_dwconv_hs_tay_slots(int H, int W, int C);
+hipError_t tp_dwconv_hs_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
+                              float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
+                              int pad, int in_act, int out_act, hipStream_t st);
 // prefix_project.hip: out[0] = base, out[j] = out[j-1] - (a[:, c] - fill[c]) (x) wt[c, :], c = perm[p0+j-1]
 // (base (N, Co), a (N, C), fill (C), wt (C, Co), perm (n <= C), out (cnt, N, Co); Co % 4 == 0)
 hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt, const int* perm,

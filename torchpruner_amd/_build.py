@@ -211,6 +211,7 @@ HOST_PROGRAMS = {
     "launcher_validation": ("wino4", "conv_mfma", "conv_wgrad", "winograd", "batchnorm", "weight_pack"),
     "dwconv_validation": ("dwconv",),
     "dwconv_act_validation": ("dwconv_act",),
+    "dwconv_hs_validation": ("dwconv_act",),
     "dwconv_carried_validation": ("dwconv", "batchnorm"),
     "se_validation": ("squeeze_excite",),
     "bn_hswish_validation": ("batchnorm",),

@@ -564,11 +564,12 @@ class _AttributionMetric(ABC):
             return _reject(why, f"compute_dtype={self.compute_dtype} runs the generic autocast path")
         return maybe_resnet_engine(self.model, eval_modules, self.device, grad=True, why=why)
 
-    def _mobilenet_engine(self, eval_modules, why=None, grad=False):
+    def _mobilenet_engine(self, eval_modules, why=None, grad=False, shapley=False):
         """The MobileNet engine when it is switched on (the ``mobilenet_engine`` keyword, else
         ``TORCHPRUNER_MOBILENET_ENGINE``) and serves ``eval_modules`` (eval-mode torchvision-layout
-        MobileNetV2, block ReLU6s; any differentiable criterion), else None. Switched off, it
-        leaves no rejection reason: the path is then exactly the one without it."""
+        MobileNetV2, block ReLU6s, or MobileNetV3, block ReLUs / Hardswishes, the latter not for
+        ``shapley``; any differentiable criterion), else None. Switched off, it leaves no rejection
+        reason: the path is then exactly the one without it."""
         from ..engine.fused_chain import _reject
         from ..engine.mobilenet_engine import maybe_mobilenet_engine, mobilenet_engine_default
         on = mobilenet_engine_default() if self.mobilenet_engine is None else bool(self.mobilenet_engine)
@@ -576,7 +577,7 @@ class _AttributionMetric(ABC):
             return None
         if not self._engines_allowed():
             return _reject(why, f"compute_dtype={self.compute_dtype} runs the generic autocast path")
-        return maybe_mobilenet_engine(self.model, eval_modules, self.device, grad=grad, why=why)
+        return maybe_mobilenet_engine(self.model, eval_modules, self.device, grad=grad, why=why, shapley=shapley)
 
     def _fused_engine(self, eval_modules, why=None, need_ce=True, pre_act_ok=False):
         """The fused chain engine (engine, block indices) for ``eval_modules``, else None.

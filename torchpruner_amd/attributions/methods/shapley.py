@@ -364,7 +364,7 @@ class ShapleyAttributionMetric(_AttributionMetric):
         copies of the 6x wider hidden activation are never built), and go through the rest of the
         network in ONE engine forward."""
         from ...engine.fused_chain import engine_criterion, per_sample_loss
-        eng = self._mobilenet_engine([module], why)
+        eng = self._mobilenet_engine([module], why, shapley=True)  # None for a MobileNetV3: no prefix scan behind a gate
         if eng is None:
             return None
         crit = engine_criterion(self.criterion, self.device)  # None: the fused cross-entropy kernel

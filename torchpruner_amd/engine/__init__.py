@@ -5,11 +5,13 @@ from __future__ import annotations
 import torch
 
 from .fused_chain import FusedChainEngine, Plan, build_plan, criterion_is_cross_entropy, maybe_engine
-from .mobilenet_engine import MobileNetEngine, build_mobilenet_plan, maybe_mobilenet_engine
+from .mobilenet_engine import (MobileNetEngine, MobileNetV3Engine, build_mobilenet_plan, build_mobilenet_v3_plan,
+                               maybe_mobilenet_engine)
 from .resnet_engine import ResNetEngine, build_resnet_plan, maybe_resnet_engine
 
 __all__ = ["FusedChainEngine", "Plan", "build_plan", "criterion_is_cross_entropy", "maybe_engine", "ResNetEngine",
            "build_resnet_plan", "maybe_resnet_engine", "MobileNetEngine", "build_mobilenet_plan",
+           "MobileNetV3Engine", "build_mobilenet_v3_plan",
            "maybe_mobilenet_engine", "native_logits", "invalidate"]
 
 

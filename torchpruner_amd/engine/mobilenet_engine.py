@@ -29,6 +29,11 @@ once on them.
 Channels are carried zero-padded to a multiple of 32 (``cpad``) as in the ResNet engine, whose conv
 plumbing (packing, tuner, classifier GEMMs, partial-slab arena) this engine inherits. One batch at a
 time: no two-stream pipeline, no graph replay. fp32 throughout.
+
+MobileNetV3 nets (``build_mobilenet_v3_plan`` / ``MobileNetV3Engine``, second half of this file) run
+the same way with ReLU / Hardswish units (``tpamd.dwconv_hs_*``), the squeeze-and-excitation gate
+between the depthwise output and the project conv, and a two-layer classifier; Shapley is not
+served there.
 """
 from __future__ import annotations
 
@@ -492,6 +497,362 @@ class MobileNetEngine(ResNetEngine):
         return self.logits_from(bi, self._conv(T, e["project"], ys, False, res=res))
 
 
+# ====================================================================== MobileNetV3
+# The same engine for the torchvision / models.mobilenet_v3 layout: units are (conv, BN, ReLU |
+# Hardswish), the depthwise unit runs ``tpamd.dwconv_hs_fwd`` / ``dwconv_hs_dgrad`` with the units'
+# activation codes (Hardswish keeps the pre-activation of its output for the backward: its derivative
+# cannot be read from the output), a squeeze-and-excitation gate sits between the depthwise output
+# and the project conv (the kernels of squeeze_excite.hip through ``ops.se_*``, on the padded NHWC
+# layout: a padded channel has y = 0, so its gated value and every gradient there are exact zeros),
+# and the classifier is Linear, Hardswish, Linear. Shapley prefixes are not served: a gate makes the
+# project conv's input non-linear in the channel mask, so the running rank-1 subtraction of
+# ``prefix_logits`` does not hold.
+_ACT_CODES = {nn.ReLU: 1, nn.Hardswish: 3}
+V3_SHAPLEY_REASON = ("mobilenet engine: Shapley on a MobileNetV3 is not served (a squeeze-and-excitation gate makes "
+                     "the project conv's input non-linear in the channel mask, so the prefix scan does not hold)")
+
+
+@dataclass
+class _V3Block:
+    expand: Optional[_Unit]
+    dw: _Unit
+    gate: Optional[nn.Module]
+    project: _Conv
+    shortcut: bool
+
+
+@dataclass
+class MobileNetV3Plan:
+    stem: _Unit
+    head: _Unit
+    fc1: nn.Linear
+    fc: nn.Linear
+    blocks: list = field(default_factory=list)
+
+
+def _act_code(act) -> int:
+    return _ACT_CODES[type(act)]
+
+
+def _unit_v3(seq, what):
+    """(_Unit, "") of a conv-BN-(ReLU | Hardswish) Sequential, else (None, reason)."""
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        return None, f"{what}: expected a (conv, BN, ReLU | Hardswish) Sequential"
+    conv, bn, act = seq
+    kind = _conv_kind(conv)
+    if kind not in ("dense", "depthwise"):
+        return None, f"{what}: {kind}"
+    if not isinstance(bn, nn.BatchNorm2d) or bn.running_mean is None:
+        return None, f"{what}: expected a BatchNorm2d with running statistics after the conv"
+    if type(act) not in _ACT_CODES:
+        return None, f"{what}: activation {type(act).__name__} is not supported (only ReLU and Hardswish)"
+    return _Unit(conv, bn, act), ""
+
+
+def _gate_reason(gate, hidden: int) -> str:
+    """"" for a gate the kernels of squeeze_excite.hip compute (``engine.train.se_eligible``) on
+    ``hidden`` channels, else why not."""
+    from .train import _se_gate_code
+    if _se_gate_code(gate) is None:
+        inner = ", ".join(f"{n} {type(getattr(gate, n, None)).__name__}" for n in ("avgpool", "activation",
+                                                                                   "scale_activation"))
+        return f"unsupported gate ({inner}; needs a global average pool, a ReLU and a Hardsigmoid or Sigmoid)"
+    if gate.fc1.weight.shape[1] != hidden or gate.fc2.weight.shape[1] != gate.fc1.weight.shape[0]:
+        return "the gate's fc widths do not chain with the block's hidden width"
+    if hidden + gate.fc1.weight.shape[0] > ops.se.SE_MAX_FC:
+        return f"the gate's widths exceed {ops.se.SE_MAX_FC}"
+    return ""
+
+
+def build_mobilenet_v3_plan(model: nn.Module):
+    """Lower a torchvision-layout MobileNetV3 (``models.mobilenet_v3``), or return (None, reason).
+    Structural: widths are read from the tensors."""
+    from ..utils.graph import is_channel_gate
+    feats, cls = getattr(model, "features", None), getattr(model, "classifier", None)
+    if not isinstance(feats, nn.Sequential) or len(feats) < 3 or cls is None or \
+            not any(isinstance(getattr(m, "block", None), nn.Sequential) for m in feats):
+        return None, "not a torchvision-layout MobileNetV3 (features / inverted-residual `.block`s / classifier)"
+    pool = getattr(model, "avgpool", None)
+    if pool is not None and not (isinstance(pool, nn.AdaptiveAvgPool2d) and pool.output_size in (1, (1, 1))):
+        return None, "avgpool: unsupported pool before the classifier (needs a global AdaptiveAvgPool2d)"
+    layers = list(cls.children()) if isinstance(cls, nn.Sequential) else [cls]
+    if len(layers) < 3 or not isinstance(layers[0], nn.Linear) or type(layers[1]) is not nn.Hardswish or \
+            not isinstance(layers[-1], nn.Linear) or not all(isinstance(m, nn.Dropout) for m in layers[2:-1]):
+        return None, "classifier: unsupported shape (needs Linear, Hardswish, Dropout layers, Linear)"
+    stem, why = _unit_v3(feats[0], "features.0 (stem)")
+    if stem is None:
+        return None, why
+    if _conv_kind(stem.conv) != "dense" or stem.conv.weight.shape[2] != 3 or stem.conv.weight.shape[1] > 4 or \
+            stem.conv.padding[0] != 1 or type(stem.act) is not nn.Hardswish:
+        return None, "features.0 (stem): needs a 3x3 conv, padding 1, of at most 4 input channels, BN and Hardswish"
+    last = len(feats) - 1
+    head, why = _unit_v3(feats[-1], f"features.{last} (head)")
+    if head is None:
+        return None, why
+    if _conv_kind(head.conv) != "dense" or not _is_1x1(head.conv) or type(head.act) is not nn.Hardswish:
+        return None, f"features.{last} (head): needs a 1x1 conv, BN and Hardswish"
+    plan = MobileNetV3Plan(stem, head, layers[0], layers[-1])
+    width = stem.conv.weight.shape[0]
+    for i, blk in enumerate(feats[1:-1], 1):
+        what = f"features.{i}"
+        seq = getattr(blk, "block", None)
+        shape = "([1x1-BN-act,] depthwise-BN-act, [gate,] (1x1, BN))"
+        if not isinstance(seq, nn.Sequential) or not 2 <= len(seq) <= 4:
+            return None, f"{what}: expected an inverted-residual `.block` {shape}"
+        items = list(seq)
+        proj = items.pop()
+        gate = items.pop() if len(items) > 1 and is_channel_gate(items[-1]) else None
+        if not items or len(items) > 2 or not isinstance(proj, nn.Sequential) or len(proj) != 2:
+            return None, f"{what}: expected an inverted-residual `.block` {shape}"
+        expand = None
+        if len(items) == 2:
+            expand, why = _unit_v3(items[0], f"{what}.block.0 (expand)")
+            if expand is None:
+                return None, why
+            if _conv_kind(expand.conv) != "dense" or not _is_1x1(expand.conv):
+                return None, f"{what}.block.0: the expand conv must be a dense 1x1 conv"
+        di = len(items) - 1
+        dw, why = _unit_v3(items[-1], f"{what}.block.{di} (depthwise)")
+        if dw is None:
+            return None, why
+        k, s, pd = dw.conv.weight.shape[2], dw.conv.stride[0], dw.conv.padding[0]
+        if _conv_kind(dw.conv) != "depthwise" or k not in (3, 5) or s not in (1, 2) or pd > k - 1:
+            return None, (f"{what}.block.{di}: the depthwise conv must be 3x3 / 5x5, stride 1 / 2, padding < k, "
+                          "depth multiplier 1")
+        hidden = dw.conv.weight.shape[0]
+        if gate is not None:
+            why = _gate_reason(gate, hidden)
+            if why:
+                return None, f"{what}.block.{di + 1}: {why}"
+        pconv, pbn = proj
+        kind = _conv_kind(pconv)
+        if kind != "dense" or not _is_1x1(pconv):
+            return None, f"{what}: the project conv must be a dense 1x1 conv" + ("" if kind == "dense" else f" ({kind})")
+        if not isinstance(pbn, nn.BatchNorm2d) or pbn.running_mean is None:
+            return None, f"{what}: expected a BatchNorm2d with running statistics after the project conv"
+        if (expand.conv.weight.shape[:2] if expand else (hidden, width)) != (hidden, width) or \
+                pconv.weight.shape[1] != hidden:
+            return None, f"{what}: channel counts of the block's convs do not chain"
+        cout = pconv.weight.shape[0]
+        shortcut = getattr(blk, "use_res_connect", None)
+        if shortcut is None:
+            shortcut = s == 1 and cout == width
+        if shortcut and (s != 1 or cout != width):
+            return None, f"{what}: a shortcut needs stride 1 and equal widths"
+        plan.blocks.append(_V3Block(expand, dw, gate, _Conv(pconv, pbn), bool(shortcut)))
+        width = cout
+    if head.conv.weight.shape[1] != width or plan.fc1.weight.shape[1] != head.conv.weight.shape[0] or \
+            plan.fc.weight.shape[1] != plan.fc1.weight.shape[0]:
+        return None, "channel counts of the head / classifier do not chain"
+    return plan, ""
+
+
+def _hs_slope(v: torch.Tensor) -> torch.Tensor:
+    """Hardswish's derivative at the pre-activation v (the branch order of dwconv_act.hip)."""
+    return torch.where(v < -3.0, torch.zeros_like(v), torch.where(v <= 3.0, v / 3.0 + 0.5, torch.ones_like(v)))
+
+
+class MobileNetV3Engine(MobileNetEngine):
+    shapley = False  # attributions/methods/shapley.py: the generic path serves these nets
+
+    def eval_modules(self):
+        """The ReLU / Hardswish modules the engine scores: per block the post-expand one (where the
+        block expands) and the post-depthwise one (before the gate)."""
+        return super().eval_modules()
+
+    def _params_key(self):
+        key = list(super()._params_key())
+        extra = [self.plan.fc1.weight, self.plan.fc1.bias]
+        for b in self.plan.blocks:
+            if b.gate is not None:
+                extra += [b.gate.fc1.weight, b.gate.fc1.bias, b.gate.fc2.weight, b.gate.fc2.bias]
+        key += [(t.data_ptr(), t._version, tuple(t.shape)) for t in extra if t is not None]
+        return tuple(key)
+
+    # ------------------------------------------------------------------ packing
+    @torch.no_grad()
+    def _pack_gate(self, gate):
+        """fc1 / fc2 as (Cs, C_padded) / (C_padded, Cs) matrices with zero columns / rows and a zero
+        fc2 bias under the padding."""
+        from .train import _se_gate_code
+        w1, w2 = gate.fc1.weight.detach().float(), gate.fc2.weight.detach().float()
+        cs, c = w1.shape[:2]
+        cp = cpad(c)
+        w1, w2 = F.pad(w1.reshape(cs, c), (0, cp - c)), F.pad(w2.reshape(c, cs), (0, 0, 0, cp - c))
+        b1 = gate.fc1.bias.detach().float() if gate.fc1.bias is not None else torch.zeros(cs, device=w1.device)
+        b2 = gate.fc2.bias.detach().float() if gate.fc2.bias is not None else torch.zeros(c, device=w1.device)
+        return {"w1": w1.contiguous(), "b1": b1.contiguous(), "w2": w2.contiguous(),
+                "b2": F.pad(b2, (0, cp - c)).contiguous(), "code": _se_gate_code(gate)}
+
+    def _pack(self):
+        key = self._params_key()
+        if key == self._key:
+            return self._packed
+        p = self.plan
+        blocks = []
+        for b in p.blocks:
+            blocks.append({"expand": self._pack_conv(b.expand) if b.expand is not None else None,
+                           "dw": self._pack_dw(b.dw), "gate": self._pack_gate(b.gate) if b.gate is not None else None,
+                           "project": self._pack_conv(b.project)})
+
+        def fc(lin, pad_out):
+            w = lin.weight.detach().float()
+            n, c = w.shape
+            npad = cpad(n) if pad_out else n
+            w = F.pad(w, (0, cpad(c) - c, 0, npad - n))
+            b = lin.bias.detach().float() if lin.bias is not None else torch.zeros(n, device=w.device)
+            wt = F.pad(w, (0, 0, 0, cpad(npad) - npad)).t().contiguous()  # backward operand: (C, outputs padded to 32)
+            return w.contiguous(), F.pad(b, (0, npad - n)).contiguous(), wt
+
+        w1, b1, wt1 = fc(p.fc1, True)
+        w2, b2, wt2 = fc(p.fc, False)
+        self._packed = {"stem": self._pack_conv(p.stem, stem=True), "blocks": blocks, "head": self._pack_conv(p.head),
+                        "fc1": {"fc_w": w1, "fc_b": b1, "fc_wt": wt1}, "fc_w": w2, "fc_b": b2, "fc_wt": wt2}
+        self._key = key
+        return self._packed
+
+    # ------------------------------------------------------------------ forward
+    def _block(self, T, blk, e, h, in_act, apoz=None, saved=None):
+        """One block from its (linear, or for a fused stem pre-activation) input ``h``; appends
+        (input, z, y, input activation code, pre-activation of y or None, gate state or None) to
+        ``saved``."""
+        apoz = apoz or {}
+        if blk.expand is not None:
+            z = self._conv(T, e["expand"], h, False, apoz=apoz.get(blk.expand.act))
+            in_act = _act_code(blk.expand.act)
+        else:
+            z = h
+        d = e["dw"]
+        out_act = _act_code(blk.dw.act)
+        pre = None
+        if saved is not None and out_act == 3:
+            s_, pd, k = d["stride"], d["pad"], d["w"].shape[2]
+            pre = z.new_empty(z.shape[0], (z.shape[1] + 2 * pd - k) // s_ + 1, (z.shape[2] + 2 * pd - k) // s_ + 1,
+                              z.shape[3])
+        y = T.dwconv_hs_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, out_act,
+                            apoz.get(blk.dw.act), pre)
+        gate, yg = None, y
+        if blk.gate is not None:
+            q = e["gate"]
+            hh, sg = ops.se_gate_fwd(ops.se_pool(y), q["w1"], q["b1"], q["w2"], q["b2"], q["code"])
+            yg = ops.se_scale(y, sg)
+            gate = (hh, sg)
+        out = self._conv(T, e["project"], yg, False, res=h if blk.shortcut else None)
+        if saved is not None:
+            saved.append((h, z, y, in_act, pre, gate))
+        return out
+
+    def _stem_out(self, T, P, x):
+        """(the first block's input, its activation code): the stem's pre-activation for a block
+        whose depthwise conv applies the Hardswish itself, else the activated output."""
+        h = T.nchw_to_nhwc_pad(x.float().contiguous(), 4)
+        h = self._conv(T, P["stem"], h, False)
+        if self._stem_fused():
+            return h, None, 3
+        return F.hardswish(h), h, 0
+
+    def _head(self, T, P, h):
+        zh = self._conv(T, P["head"], h, False)
+        feat = T.avgpool_nhwc(F.hardswish(zh))
+        z1 = self._fc(T, P["fc1"], feat)
+        return self._fc(T, P, F.hardswish(z1)), zh, z1
+
+    def forward(self, x: torch.Tensor, apoz: Optional[dict] = None, save: bool = False):
+        """As :meth:`MobileNetEngine.forward`; the last entry of ``saved`` is (head pre-activation,
+        classifier pre-activation, stem pre-activation)."""
+        T = ops.require()
+        P = self._pack()
+        apoz = dict(apoz or {})
+        padded = []
+        for m, buf in apoz.items():
+            if buf.shape[1] % 32:
+                tmp = buf.new_zeros(buf.shape[0], cpad(buf.shape[1]))
+                padded.append((buf, tmp))
+                apoz[m] = tmp
+        h, z0, in_act = self._stem_out(T, P, x)
+        if z0 is None:
+            z0 = h
+        saved = []
+        for blk, e in zip(self.plan.blocks, P["blocks"]):
+            h = self._block(T, blk, e, h, in_act, apoz, saved if save else None)
+            in_act = 0
+        logits, zh, z1 = self._head(T, P, h)
+        for buf, tmp in padded:
+            buf.add_(tmp[:, :buf.shape[1]])
+        if save:
+            saved.append((zh, z1, z0))
+            return logits, saved
+        return logits
+
+    # ------------------------------------------------------------------ backward (Taylor, Sensitivity)
+    def grad_scores(self, x: torch.Tensor, y: torch.Tensor, want, mode: str, criterion=None,
+                    loss_batch: Optional[int] = None, raw_slabs: bool = False):
+        """As :meth:`MobileNetEngine.grad_scores`. A gated block's post-depthwise score is reduced
+        from (y, dL/dy) after the gate's backward (dL/dy = g * s + dp / HW: through the scale and
+        through the pooled mean)."""
+        T = ops.require()
+        P = self._pack()
+        logits, saved = self.forward(x, save=True)
+        zh, z1, _ = saved.pop()
+        B = logits.shape[0]
+        blocks = self.plan.blocks
+        first = min((bi for bi, b in enumerate(blocks)
+                     if b.dw.act in want or (b.expand is not None and b.expand.act in want)), default=None)
+        out = {}
+        if first is None:
+            return out
+        g_log = logits_grad(logits, y, criterion, loss_batch)
+        # classifier: Linear, Hardswish, Linear (the GEMM kernel's mask operand is all ones: no ReLU here)
+        g1 = self._fc_bwd(T, P, g_log, torch.ones_like(z1)) * _hs_slope(z1)
+        g_feat = self._fc_bwd(T, P["fc1"], g1, zh.new_ones(B, zh.shape[3]))
+        HW = zh.shape[1] * zh.shape[2]
+        g = (g_feat / HW)[:, None, None, :] * _hs_slope(zh)  # avg-pool backward + the head's Hardswish
+        g, _ = self._dgrad(T, P["head"], g.contiguous(), None)
+        akey = (tuple(x.shape), mode, tuple(sorted(i for i, m in enumerate(self.eval_modules()) if m in want)))
+        size = self._arena_sizes.get(akey)
+        arena = [torch.zeros(size, device=x.device) if size else None, 0, 0]
+        for bi in range(len(blocks) - 1, first - 1, -1):
+            blk, e = blocks[bi], P["blocks"][bi]
+            h, z, yd, in_act, pre, gate = saved[bi]
+            gy, _ = self._dgrad(T, e["project"], g, None)  # dL/d(project input), unfactored
+            if gate is not None:
+                q, (hh, sg) = e["gate"], gate
+                _, _, dp = ops.se_gate_bwd(ops.se_bwd_reduce(gy, yd), sg, hh, q["w1"], q["w2"], q["code"])
+                gy = ops.se_bwd_dx(gy, sg, dp)  # dL/d(depthwise activation output)
+            if blk.dw.act in want:
+                out[blk.dw.act] = ops.channel_reduce(yd.permute(0, 3, 1, 2), gy.permute(0, 3, 1, 2), mode)
+            ex_wanted = blk.expand is not None and blk.expand.act in want
+            if bi == first and not ex_wanted:
+                break
+            d = e["dw"]
+            _, H, W, C = z.shape
+            tay = self._slab(arena, T.dwconv_hs_tay_slots(H, W, C), B, C, x.device) if ex_wanted else None
+            out_act = _act_code(blk.dw.act)
+            dz = T.dwconv_hs_dgrad(gy, pre if out_act == 3 else yd, d["w"], d["scale"], z, H, W, d["stride"], d["pad"],
+                                   in_act, out_act, tay, _TAY_MODES[mode])
+            if ex_wanted:
+                if raw_slabs:
+                    out[blk.expand.act] = tay
+                else:
+                    sums = tay.sum(0)
+                    out[blk.expand.act] = sums.abs_() if mode == "taylor" else sums
+            if bi == first:
+                break
+            if blk.expand is not None:  # the block input is linear: no factor
+                g, _ = self._dgrad(T, e["expand"], dz, None, res=g if blk.shortcut else None)
+            else:
+                g = dz + g if blk.shortcut else dz
+        if arena[2] > (size or 0):
+            self._arena_sizes[akey] = arena[2]
+        return out
+
+    # ------------------------------------------------------------------ Shapley: not served
+    def forward_to(self, *a, **k):
+        raise NotImplementedError(V3_SHAPLEY_REASON)
+
+    prefix_logits = logits_from = block_logits = prefix_fill = forward_to
+
+
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
 
 
@@ -500,28 +861,43 @@ def mobilenet_engine_default() -> bool:
     return os.environ.get("TORCHPRUNER_MOBILENET_ENGINE", "0") not in ("0", "")
 
 
-def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None):
-    """A MobileNetEngine when every eval module is a block ReLU6 the engine serves, else None
-    (``why`` receives the reason). ``grad`` is accepted for symmetry with the ResNet engine: the
-    same modules are served forward (APoZ) and backward (Taylor, Sensitivity)."""
+def _engine_sig(eng):
+    return (type(eng), [c.conv for c in eng._all_convs()], [b.shortcut for b in eng.plan.blocks],
+            [getattr(b, "gate", None) for b in eng.plan.blocks])
+
+
+def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, shapley=False):
+    """A MobileNetEngine (MobileNetV2 layout) or MobileNetV3Engine when every eval module is a block
+    activation the engine serves, else None (``why`` receives the reason). ``grad`` is accepted for
+    symmetry with the ResNet engine: the same modules are served forward (APoZ) and backward
+    (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation, which a MobileNetV3 does
+    not get (``V3_SHAPLEY_REASON``)."""
     from .fused_chain import _reject, engines_enabled
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if not engines_enabled():
         return _reject(why, "mobilenet engine: engines disabled (TORCHPRUNER_ENGINES=0)")
+    if shapley and build_mobilenet_plan(model)[0] is None and build_mobilenet_v3_plan(model)[0] is not None:
+        return _reject(why, V3_SHAPLEY_REASON)
     if dev.type != "cuda" or ops.backend() == "torch" or not ops.available() or model.training:
         return _reject(why, "mobilenet engine: needs an eval-mode model on a GPU with the native extension")
     if any(p.dtype != torch.float32 for p in model.parameters()):
         return _reject(why, "mobilenet engine: parameters are not float32")
     plan, reason = build_mobilenet_plan(model)  # re-validated every run: pruning changes channel counts
+    cls = MobileNetEngine
     if plan is None:
-        return _reject(why, f"mobilenet engine: {reason}")
+        plan, reason3 = build_mobilenet_v3_plan(model)
+        cls = MobileNetV3Engine
+        if plan is None:  # the reason of the layout the model looks like
+            v3 = any(isinstance(getattr(m, "block", None), nn.Sequential) for m in getattr(model, "features", []))
+            return _reject(why, f"mobilenet engine: {reason3 if v3 else reason}")
+    new = cls(model, plan)
     eng = _ENGINES.get(model)
-    if eng is None or [c.conv for c in eng._all_convs()] != [c.conv for c in MobileNetEngine(model, plan)._all_convs()] \
-            or [b.shortcut for b in eng.plan.blocks] != [b.shortcut for b in plan.blocks]:
-        eng = MobileNetEngine(model, plan)
+    if eng is None or _engine_sig(eng) != _engine_sig(new):
+        eng = new
         _ENGINES[model] = eng
     ok = set(map(id, eng.eval_modules()))
     if not all(id(m) in ok for m in eval_modules):
-        return _reject(why, "mobilenet engine: evaluation modules must be the ReLU6 after a block's expand or "
-                            "depthwise conv (use find_best_evaluation_module=True)")
+        return _reject(why, "mobilenet engine: evaluation modules must be the activation (ReLU6; ReLU / Hardswish "
+                            "of a MobileNetV3) after a block's expand or depthwise conv (use "
+                            "find_best_evaluation_module=True)")
     return eng

@@ -259,3 +259,103 @@ def mobilenet_scores_fp64(engine, model, x, y, mode="taylor", conditioned=True, 
         v = v.flatten(2).sum(-1)
         scores[o] = v.abs() if mode == "taylor" else v
     return scores, flips, totals
+
+
+def mobilenet_v3_scores_fp64(engine, model, x, y, mode="taylor", conditioned=True, criterion=None):
+    """fp64 oracle of the MobileNetV3 engine's scores on one batch, as :func:`mobilenet_scores_fp64`:
+    a CPU autograd pass of a float64 copy of ``model`` (every activation out of place), scored at
+    the modules the engine serves (``MobileNetV3Engine.eval_modules``).
+
+    ``conditioned=True`` replays the engine's own branch decision of EVERY piecewise activation of
+    the net, read from the tensors its fp32 forward saved: a ReLU's ``<= 0`` or live (the gates'
+    inner ReLU included), a Hardswish's ``< -3``, middle or ``> 3`` (stem, blocks, head, classifier)
+    and a Hardsigmoid gate's ``<= 0``, middle or ``>= 1``. The fp64 pass evaluates the formula of
+    the engine's branch at its own fp64 pre-activation (0, v (v + 3) / 6 or v; 0, v / 6 + 0.5 or
+    1): the activations are continuous, so the value moves by rounding only while autograd
+    differentiates the engine's branch. ``conditioned=False`` is the plain fp64 run (``engine`` may
+    be None).
+
+    Returns (scores, flips, totals) as :func:`mobilenet_scores_fp64` does, for
+    :func:`flip_violations`."""
+    import copy
+
+    import torch.nn as nn
+    from .mobilenet_engine import build_mobilenet_v3_plan
+    assert engine is not None or not conditioned, "replaying decisions needs the engine"
+    m64 = copy.deepcopy(model).double().cpu().eval()
+    names = {id(m): n for n, m in m64.named_modules()}
+    twin = {id(o): c for o, c in zip(model.modules(), m64.modules())}
+    kinds = (nn.ReLU, nn.Hardswish, nn.Hardsigmoid)
+    acts = [m for m in m64.modules() if type(m) in kinds]
+    for m in acts:
+        m.inplace = False
+    decided = {}  # activation of the copy -> engine tensor holding its decision
+    if engine is not None:
+        with torch.no_grad():
+            saved = engine.forward(x, save=True)[1]
+        zh, z1, z0 = saved[-1]
+        plan = engine.plan
+        decided[twin[id(plan.stem.act)]] = z0
+        decided[twin[id(plan.head.act)]] = zh
+        decided[twin[id(list(model.classifier.children())[1])]] = z1
+        for blk, (_, z, yd, _, pre, gate) in zip(plan.blocks, saved[:-1]):
+            if blk.expand is not None:
+                decided[twin[id(blk.expand.act)]] = z
+            decided[twin[id(blk.dw.act)]] = pre if pre is not None else yd  # a ReLU's output has its regions
+            if gate is not None:
+                decided[twin[id(blk.gate.activation)]] = gate[0]
+                if type(blk.gate.scale_activation) is nn.Hardsigmoid:
+                    decided[twin[id(blk.gate.scale_activation)]] = gate[1]
+    flips, totals, outs = {}, {}, {}
+    zero, one = torch.zeros((), dtype=torch.float64), torch.ones((), dtype=torch.float64)
+
+    def hook(mod, inp, out):
+        z = inp[0]
+        t = decided.get(mod)
+        if t is not None:
+            c = z.shape[1]
+            tf = _nchw(t, c) if t.dim() == 4 else t[:, :c].double().cpu().reshape(z.shape)
+            if type(mod) is nn.ReLU:
+                lo_f, hi_f, lo, hi = tf <= 0, None, z <= 0, None
+                branch = z
+            elif type(mod) is nn.Hardswish:
+                lo_f, hi_f, lo, hi = tf < -3, tf > 3, z < -3, z > 3
+                branch = torch.where(hi_f, z, z * (z + 3.0) / 6.0)
+            else:  # Hardsigmoid: the engine keeps its output s
+                lo_f, hi_f, lo, hi = tf <= 0, tf >= 1, z <= -3, z >= 3
+                branch = torch.where(hi_f, one, z / 6.0 + 0.5)
+            diff = lo_f != lo
+            if hi_f is not None:
+                diff = diff | (hi_f != hi)
+            flips[names[id(mod)]] = int(diff.sum())
+            totals[names[id(mod)]] = z.numel()
+            if conditioned:
+                out = torch.where(lo_f, zero, branch)
+        outs[mod] = out
+        if out.requires_grad:
+            out.retain_grad()
+        return out
+
+    handles = [m.register_forward_hook(hook) for m in acts]
+    try:
+        with torch.enable_grad():
+            xin = x.detach().double().cpu().requires_grad_(True)  # keeps every activation in the graph
+            logits = m64(xin)
+            loss = F.cross_entropy(logits, y.cpu()) if criterion is None else criterion(logits, y.cpu())
+            loss.backward()
+    finally:
+        for h in handles:
+            h.remove()
+    if engine is not None:
+        served = engine.eval_modules()
+    else:
+        plan, why = build_mobilenet_v3_plan(model)
+        assert plan is not None, why
+        served = [a for b in plan.blocks for a in (([b.expand.act] if b.expand is not None else []) + [b.dw.act])]
+    scores = {}
+    for o in served:
+        a, g = outs[twin[id(o)]].detach(), outs[twin[id(o)]].grad
+        v = g.abs() if mode == "sensitivity" else -(g * a)
+        v = v.flatten(2).sum(-1)
+        scores[o] = v.abs() if mode == "taylor" else v
+    return scores, flips, totals

@@ -13,6 +13,7 @@ import torch
 from ._native import available, backend, load, require, use_native
 from .bn_hswish import bn_hswish_bwd, bn_hswish_fwd
 from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
+from .dwconv_hs import dwconv_hs_dgrad, dwconv_hs_fwd, dwconv_hs_tay_slots
 from .se import SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_bwd, se_gate_fwd, se_pool, se_scale, se_wgrad
 
 __all__ = [
@@ -20,6 +21,7 @@ __all__ = [
     "REDUCE_MODES", "channel_reduce", "column_accumulate", "score_fold_", "channel_fill_", "nan_channels",
     "gather_multi", "prefix_mask", "prefix_project", "shapley_scatter", "shapley_column", "cross_entropy",
     "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
+    "dwconv_hs_fwd", "dwconv_hs_dgrad", "dwconv_hs_tay_slots",
     "SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad",
     "bn_hswish_fwd", "bn_hswish_bwd",
 ]

@@ -19,14 +19,15 @@ import logging
 
 import torch
 import torch.nn as nn
-from torch.nn.modules.activation import LeakyReLU, ReLU, ReLU6, RReLU, Sigmoid, Softplus, Tanh
+from torch.nn.modules.activation import Hardswish, LeakyReLU, ReLU, ReLU6, RReLU, Sigmoid, Softplus, Tanh
 from torch.nn.modules.batchnorm import _BatchNorm
 from torch.nn.modules.conv import _ConvNd
 from torch.nn.modules.dropout import _DropoutNd
 
 logger = logging.getLogger("torchpruner")
 
-ACTIVATIONS = (ReLU, ReLU6, RReLU, LeakyReLU, Sigmoid, Softplus, Tanh)
+# (Hardswish: the unit activation of MobileNetV3; scored after it like a ReLU6 of MobileNetV2)
+ACTIVATIONS = (ReLU, ReLU6, RReLU, LeakyReLU, Sigmoid, Softplus, Tanh, Hardswish)
 
 
 def _dense_fc(m) -> bool:
