@@ -282,9 +282,16 @@ at::Tensor prefix_delta(const at::Tensor& T, const at::Tensor& wsub, const at::T
   need(y0, "y0", 2, &T);
   const int64_t M = T.size(0), Kc = T.size(1), N = wsub.size(0), B0 = y0.size(0);
   TORCH_CHECK(wsub.size(1) == Kc && y0.size(1) == N, "shape mismatch: T (M, Kc), wsub (N, Kc), y0 (B0, N)");
+  TORCH_CHECK(M > 0 && Kc > 0 && N > 0 && B0 > 0, "empty operand: T (", M, ", ", Kc, "), y0 (", B0, ", ", N, ")");
+  TORCH_CHECK(M < (1ll << 31) && Kc < (1ll << 31) && N < (1ll << 31), "operand sizes are 32-bit");
   TORCH_CHECK(Kc % 32 == 0 && N % 4 == 0 && M % B0 == 0, "need Kc % 32 == 0, N % 4 == 0, M % B0 == 0");
   TORCH_CHECK(cfg >= 0 && cfg <= 6, "bad tile config");
+  TORCH_CHECK(neg_one.defined(), "neg_one must be the (N,) scale vector");
   const float* no = opt_ptr(neg_one, N, "neg_one", T);
+  // float4 operand loads and epilogue reads: a contiguous view at an odd offset must not reach the kernel
+  for (const at::Tensor* t : {&T, &wsub, &y0})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr<float>()) % 16 == 0,
+                "T, wsub and y0 must be 16-byte aligned");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(T.device());
   auto out = at::empty({M, N}, T.options());
   TP_CHECK_HIP(tp_prefix_delta_gemm(T.data_ptr<float>(), wsub.data_ptr<float>(), no, y0.data_ptr<float>(), (int)M,

@@ -1679,6 +1679,11 @@ extern "C" hipError_t tp_prefix_delta_gemm(const float* T, const float* Wsub, co
                                            int M, int Kc, int N, int B0, int relu, float slope, int cfg,
                                            float* out, hipStream_t st) {
   using namespace tp;
+  if (!T || !Wsub || !neg_one || !Y0 || !out || M <= 0 || Kc <= 0 || N <= 0) return hipErrorInvalidValue;
+  if (cfg < 0 || cfg > 6) return hipErrorInvalidValue;  // plain tile configs only: no stream-K / single-buffer flag
+  // float4 operand loads, float4 epilogue reads of Y0 / neg_one and float4 stores of out
+  if (((uintptr_t)T | (uintptr_t)Wsub | (uintptr_t)neg_one | (uintptr_t)Y0 | (uintptr_t)out) % 16 != 0)
+    return hipErrorInvalidValue;
   if (Kc % 32 != 0 || N % 4 != 0 || B0 <= 0 || M % B0 != 0 || !(slope >= 0.f)) return hipErrorInvalidValue;
   ConvArgs a{};
   a.x = T;
@@ -1693,7 +1698,8 @@ extern "C" hipError_t tp_prefix_delta_gemm(const float* T, const float* Wsub, co
   a.stride = 1;
   a.pad = 0;
   a.x_elems = (long long)M * Kc;
-  if (a.x_elems * 4 >= (1ll << 31) || (long long)M * N * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+  if (a.x_elems * 4 >= (1ll << 31) || (long long)N * Kc * 4 >= (1ll << 31) || (long long)M * N * 4 >= (1ll << 31))
+    return hipErrorInvalidValue;
   a.k_tiles_per_split = Kc / 32;
   a.scale = neg_one;
   a.relu = relu;

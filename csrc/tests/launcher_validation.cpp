@@ -153,6 +153,47 @@ int main() {
          hipErrorInvalidValue);  // split-K slabs are K wide
   EXPECT(tp_conv_wino4(n, n, 2, 32, 64, 64, 0, n, n, 1, n, nullptr, n, n, n, 0, 1, n, 1, 0, nullptr, 0) ==
          hipErrorInvalidValue);  // the removed WIDE variant
+  // Shapley prefix-delta GEMM: prefix_delta_gemm(T, Wsub, neg_one, Y0, M, Kc, N, B0, relu, slope, cfg, out)
+  {
+    const hipError_t BAD = hipErrorInvalidValue;
+    float* A16 = reinterpret_cast<float*>(16);
+    float* A4 = reinterpret_cast<float*>(20);  // 4-byte aligned only
+    const float nanf_ = __builtin_nanf("");
+    EXPECT(tp_prefix_delta_gemm(nullptr, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, nullptr, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, nullptr, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, nullptr, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, nullptr, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 0, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);    // M = 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, -160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // M < 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 0, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);   // Kc = 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, -32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // Kc < 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 0, 5, 1, 0.01f, 0, A16, nullptr) == BAD);   // N = 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, -12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // N < 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, -1, A16, nullptr) == BAD);  // cfg
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 7, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 32 | 2, A16, nullptr) == BAD);  // stream-K
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 64 | 2, A16, nullptr) == BAD);  // one stage
+    EXPECT(tp_prefix_delta_gemm(A4, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // alignment
+    EXPECT(tp_prefix_delta_gemm(A16, A4, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A4, A16, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A4, 160, 32, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, 0.01f, 0, A4, nullptr) == BAD);
+    // the checks the launcher already had
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 40, 12, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // Kc % 32
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 10, 5, 1, 0.01f, 0, A16, nullptr) == BAD);  // N % 4
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 0, 1, 0.01f, 0, A16, nullptr) == BAD);  // B0 = 0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, -5, 1, 0.01f, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 7, 1, 0.01f, 0, A16, nullptr) == BAD);  // M % B0
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, -0.01f, 0, A16, nullptr) == BAD);  // slope
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 160, 32, 12, 5, 1, nanf_, 0, A16, nullptr) == BAD);
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 1 << 20, 512, 12, 1, 1, 0.01f, 0, A16, nullptr) ==
+           BAD);  // T: 2^31 bytes
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 5, 1 << 14, 1 << 15, 5, 1, 0.01f, 0, A16, nullptr) ==
+           BAD);  // Wsub: 2^31 bytes
+    EXPECT(tp_prefix_delta_gemm(A16, A16, A16, A16, 1 << 15, 32, 1 << 14, 1, 1, 0.01f, 0, A16, nullptr) ==
+           BAD);  // out: 2^31 bytes
+  }
   EXPECT(tp_pack_conv_weights_multi(nullptr, 0, 16, nullptr) == hipErrorInvalidValue);  // no operands
   EXPECT(tp_pack_conv_weights_multi(nullptr, 2, 0, nullptr) == hipErrorInvalidValue);   // nothing to write
   EXPECT(tp_wino4_weights_multi(nullptr, 1, 100, nullptr) == hipErrorInvalidValue);     // not whole blocks

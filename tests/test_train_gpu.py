@@ -555,8 +555,15 @@ def test_bottleneck_backward_fusions(cuda):
     from the next block's conv1 dgrad epilogue and identity gradients reach conv1's epilogue unmasked
     (masked there by the tail's ReLU bits). Gradients vs fp64 autograd on the same model, and both
     fusions were taken; a second consumer of a block output (a tail hook adding to its gradient) makes
-    the tail fall back to its own statistics pass, still exact."""
+    the tail fall back to its own statistics pass, still exact.
+
+    The kernel choices are the untimed ones (``TUNER.fixed()``): this net ends in BatchNorms over 4 samples
+    of 2x2 and 1x1 maps, which amplify forward rounding a few thousand times, so whether the 5e-3 bound held
+    depended on which kernel the timing picked on the box. With the F(4x4) Winograd forward at layer2's 8x8
+    3x3 convs (4e-6 relative error in the conv output against fp64, 3e-7 for the implicit GEMM)
+    conv1.weight missed it by 2.7x, with the fusions on or off."""
     from torchpruner_amd.engine import train as tr
+    from torchpruner_amd.engine.fused_chain import TUNER
     from torchpruner_amd.models.resnet import Bottleneck, ResNet
     if not tr._BWD_FUSE:
         pytest.skip("TORCHPRUNER_BN_BWD_FUSE=0")
@@ -583,7 +590,7 @@ def test_bottleneck_backward_fusions(cuda):
         model.zero_grad(set_to_none=True)
         feats = {}
         h = model.layer2[0].register_forward_hook(lambda m, i, o: feats.__setitem__("o", o))
-        with tr.native_convs(model):
+        with TUNER.fixed(), tr.native_convs(model):
             loss = F.cross_entropy(model(x), y)
             if extra:  # a second consumer of a block output
                 loss = loss + (feats["o"] ** 2).mean() * 1e-2
