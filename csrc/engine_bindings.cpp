@@ -710,8 +710,13 @@ at::Tensor conv_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t ks, int6
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = g.size(3);
   TORCH_CHECK(Cin % 4 == 0 && Cout % 4 == 0, "conv_wgrad needs Cin % 4 == 0 and Cout % 4 == 0");
   TORCH_CHECK(ks >= 1 && stride >= 1 && pad >= 0, "bad conv geometry");
+  TORCH_CHECK(x.numel() > 0 && Cout > 0, "conv_wgrad: empty operand, x ", x.sizes(), " g ", g.sizes());
+  TORCH_CHECK(H + 2 * pad >= ks && W + 2 * pad >= ks, "conv_wgrad: a ", ks, "x", ks, " kernel on a padded map of ",
+              H + 2 * pad, "x", W + 2 * pad);
   const int64_t Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
   TORCH_CHECK(g.size(0) == B && g.size(1) == Ho && g.size(2) == Wo, "g must be (B, Ho, Wo, Cout) of this conv");
+  need_aligned16(g, "g");
+  need_aligned16(x, "x");
   const int64_t Kpad = (ks * ks * Cin + 31) / 32 * 32;
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
   const ParamOut f = present(out) ? param_out(*out, Cout, Cin, ks, g) : ParamOut();
@@ -744,12 +749,17 @@ std::tuple<at::Tensor, at::Tensor> conv_gen_stats(const at::Tensor& x, const at:
 }
 
 // Winograd F(2x2,3x3) weight gradient of a stride-1 pad-1 3x3 conv: g (B, H, W, Cout), x (B, H, W,
-// Cin) NHWC (H, W even, Cin % 32 == 0) -> ``out`` (Cout_r, Cin_r, 3, 3), any positive strides (real channels).
+// Cin) NHWC (H, W even, Cin % 4 == 0 and >= 8, Cout % 4 == 0: the GEMM pads Cin to its 32-wide K granule itself)
+// -> ``out`` (Cout_r, Cin_r, 3, 3), any positive strides (real channels).
 void wino_wgrad(const at::Tensor& g, const at::Tensor& x, int64_t cfg, int64_t splits, at::Tensor& out) {
   need(g, "g", 4);
   need(x, "x", 4, &g);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = g.size(3);
   TORCH_CHECK(g.size(0) == B && g.size(1) == H && g.size(2) == W, "g must be (B, H, W, Cout) of a same-size conv");
+  TORCH_CHECK(x.numel() > 0 && Cout > 0, "wino_wgrad: empty operand, x ", x.sizes(), " g ", g.sizes());
+  TORCH_CHECK(cfg >= 0 && cfg <= 2, "wino_wgrad: bad tile config ", cfg, " (0 .. 2)");
+  need_aligned16(g, "g");
+  need_aligned16(x, "x");
   TORCH_CHECK(H % 2 == 0 && W % 2 == 0 && Cin % 4 == 0 && Cin >= 8 && Cout % 4 == 0,
               "wino_wgrad needs even H/W, Cin % 4 (>= 8), Cout % 4");
   const ParamOut f = param_out(out, Cout, Cin, 3, g);

@@ -41,6 +41,11 @@ inline void need(const at::Tensor& t, const char* name, int64_t dim = kAnyLayout
   TORCH_CHECK(dim < 0 || t.dim() == dim, name, " must have ", dim, " dims, got ", t.dim());
 }
 
+// An operand its kernels read as float4 (a view at an odd storage offset is not).
+inline void need_aligned16(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
 // Nullable vector of exactly n elements (a short one would be read out of bounds).
 inline float* vec_ptr(const OptTensor& t, int64_t n, const char* name, const at::Tensor& like) {
   if (!present(t)) return nullptr;

@@ -244,7 +244,8 @@ hipError_t launch_wgrad(const tp::WgradArgs& a, int splits, hipStream_t st) {
 // Tile configs: 0 = 128x128 (4 waves of 64x64), 1 = 64x64 (4 waves of 32x32), 2 = 128x64
 // (4 waves of 64x32). ``ws`` holds splits*Cout*Kpad floats (may alias dw when splits == 1).
 // x (B, H, W, Cin) NHWC with Cin % 4 == 0; g (B, Ho, Wo, Cout) NHWC with Cout % 4 == 0;
-// dw (Cout, Kpad), Kpad % 32 == 0 and >= ks*ks*Cin.
+// dw (Cout, Kpad), Kpad % 32 == 0 and >= ks*ks*Cin. g, x, dw and ws 16-byte aligned, fin 4-byte; every size
+// positive, ks <= H + 2*pad and W + 2*pad, fewer than 2^31 - 31 output pixels (hipErrorInvalidValue otherwise).
 // fin (nullable): also/instead write the parameter-layout gradient (fin_co <= Cout, fin_ci <= Cin,
 // ks, ks) with element strides fs[4]; dw is then not written (may be null).
 // batch > 1: ``batch`` independent GEMMs (operands g + z*g_bstride, x + z*x_bstride) -> dw
@@ -254,10 +255,28 @@ extern "C" hipError_t tp_conv_wgrad(const float* g, const float* x, float* dw, f
                                     float* fin, int fin_co, int fin_ci, const long long* fs, int batch,
                                     long long g_bstride, long long x_bstride, hipStream_t st) {
   using namespace tp;
-  if (Cin % 4 || Cout % 4 || Kpad % 32 || Kpad < ks * ks * Cin || splits < 1) return hipErrorInvalidValue;
+  // every check before any arithmetic on the sizes: an empty batch or a zero stride used to divide by zero below
+  if (!g || !x) return hipErrorInvalidValue;
+  if ((((uintptr_t)g | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)ws) & 15) != 0 || ((uintptr_t)fin & 3) != 0)
+    return hipErrorInvalidValue;  // float4 loads of g / x, float rows of 32 in dw / ws (null passes: checked below)
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return hipErrorInvalidValue;
+  if (ks < 1 || stride < 1 || pad < 0) return hipErrorInvalidValue;
+  if (Cin % 4 || Cout % 4 || Kpad % 32 || Kpad < (long long)ks * ks * Cin || splits < 1) return hipErrorInvalidValue;
   if (batch < 1 || batch > 65535 || (batch > 1 && fin)) return hipErrorInvalidValue;
   if (fin && (fin_co > Cout || fin_ci > Cin || fin_co <= 0 || fin_ci <= 0 || !fs)) return hipErrorInvalidValue;
+  if (fin)
+    for (int i = 0; i < 4; ++i)
+      if (fs[i] <= 0) return hipErrorInvalidValue;  // a zero stride makes the kernel's writes overlap
   if (!fin && !dw) return hipErrorInvalidValue;
+  // output map: the kernel is larger than the padded map when the numerator is negative (C++ division would
+  // round it towards zero and report a map of one pixel, or a negative size whose product P is positive)
+  const long long num_h = (long long)H + 2ll * pad - ks, num_w = (long long)W + 2ll * pad - ks;
+  if (num_h < 0 || num_w < 0) return hipErrorInvalidValue;
+  const long long Ho64 = num_h / stride + 1, Wo64 = num_w / stride + 1;
+  constexpr long long P_MAX = 2147483647ll - 31;  // P + 31 is formed in 32 bits (the slice count)
+  if (Ho64 > P_MAX || Wo64 > P_MAX || (long long)B * Ho64 > P_MAX) return hipErrorInvalidValue;
+  const long long P64 = (long long)B * Ho64 * Wo64;  // both factors below 2^31: exact in 64 bits
+  if (P64 > P_MAX) return hipErrorInvalidValue;
   WgradArgs a{};
   a.batch = batch;
   a.g_bstride = g_bstride;
@@ -277,16 +296,18 @@ extern "C" hipError_t tp_conv_wgrad(const float* g, const float* x, float* dw, f
   a.ks = ks;
   a.stride = stride;
   a.pad = pad;
-  a.Ho = (H + 2 * pad - ks) / stride + 1;
-  a.Wo = (W + 2 * pad - ks) / stride + 1;
+  a.Ho = (int)Ho64;
+  a.Wo = (int)Wo64;
   a.Kc = ks * ks * Cin;
   a.Kpad = Kpad;
-  a.P = B * a.Ho * a.Wo;
+  a.P = (int)P64;
   a.fd_hwo = FastDiv((unsigned)std::max(1, a.Ho * a.Wo));
   a.fd_wo = FastDiv((unsigned)std::max(1, a.Wo));
   a.g_elems = (long long)a.P * Cout;
+  constexpr long long ELEMS_MAX = 1ll << 29;  // operands below 2^31 bytes (32-bit buffer offsets)
+  if ((long long)B * H >= ELEMS_MAX || (long long)B * H * W >= ELEMS_MAX) return hipErrorInvalidValue;
   a.x_elems = (long long)B * H * W * Cin;
-  if (a.g_elems * 4 >= (1ll << 31) || a.x_elems * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+  if (a.g_elems >= ELEMS_MAX || a.x_elems >= ELEMS_MAX) return hipErrorInvalidValue;
   const int slices = (a.P + 31) / 32;
   splits = std::min(splits, slices);
   a.slices_per_split = (slices + splits - 1) / splits;

@@ -138,18 +138,27 @@ extern "C" long long tp_wino_wgrad_ws_elems(int B, int H, int W, int Cin, int Co
 
 // g (B, H, W, Cout), x (B, H, W, Cin) NHWC; H, W even; Cin % 4 == 0 (any pruned width carried at
 // a multiple of 4), Cout % 4 == 0. Writes the (fin_co, fin_ci, 3, 3) parameter-layout gradient with
-// element strides fs.
+// element strides fs (positive). g, x and ws 16-byte aligned, fin 4-byte; every size positive; cfg 0..2, refused
+// before the transforms are launched (hipErrorInvalidValue otherwise).
 extern "C" hipError_t tp_wino_wgrad(const float* g, const float* x, float* ws, int B, int H, int W, int Cin, int Cout,
                                     int cfg, int splits, float* fin, int fin_co, int fin_ci, const long long* fs,
                                     hipStream_t st) {
   using namespace tp;
+  if (!g || !x || !ws) return hipErrorInvalidValue;
+  if ((((uintptr_t)g | (uintptr_t)x | (uintptr_t)ws) & 15) != 0 || ((uintptr_t)fin & 3) != 0)
+    return hipErrorInvalidValue;  // the transforms read and write float4
+  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return hipErrorInvalidValue;
   if ((H & 1) || (W & 1) || Cin % 4 || Cin < 8 || Cout % 4 || !fin || !fs || fin_co > Cout || fin_ci > Cin ||
-      splits < 1)
+      fin_co <= 0 || fin_ci <= 0 || splits < 1)
     return hipErrorInvalidValue;
-  const int Kp = (Cin + 31) / 32 * 32;
+  for (int i = 0; i < 4; ++i)
+    if (fs[i] <= 0) return hipErrorInvalidValue;
+  if (cfg < 0 || cfg > 2) return hipErrorInvalidValue;  // before the transforms are launched, not after
+  if ((long long)B * (H / 2) >= (1ll << 31)) return hipErrorInvalidValue;  // T below stays exact in 64 bits
   const long long T = (long long)B * (H / 2) * (W / 2);
-  if (T <= 0) return hipErrorInvalidValue;
-  if (T * Cin * 4 >= (1ll << 31) || T * Cout * 4 >= (1ll << 31) || T >= (1ll << 31)) return hipErrorInvalidValue;
+  if (T <= 0 || T >= (1ll << 31)) return hipErrorInvalidValue;
+  if (T * Cin * 4 >= (1ll << 31) || T * Cout * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+  const int Kp = (Cin + 31) / 32 * 32;  // Cin < 2^29 by now
   float* v = ws;
   float* m = v + 16 * T * Cin;
   float* du = m + 16 * T * Cout;

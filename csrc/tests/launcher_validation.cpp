@@ -88,12 +88,7 @@ int main() {
                      nullptr, nullptr, nullptr, bits, 0) == hipErrorInvalidValue);  // bnb_bits alone
   EXPECT(tp_bn_bwd_train_pre(n, n, n, 64, 8, 8, n, n, n, n, n, n, n, n, nullptr, nullptr, 0, n, n, nullptr, 0) ==
          hipErrorInvalidValue);  // no tiles
-  EXPECT(tp_conv_wgrad(n, n, n, n, 2, 8, 8, 6, 64, 3, 1, 1, 64, 0, 1, nullptr, 0, 0, nullptr, 1, 0, 0, 0) ==
-         hipErrorInvalidValue);  // Cin % 4
-  EXPECT(tp_conv_wgrad(n, n, n, n, 2, 8, 8, 64, 64, 3, 1, 1, 96, 0, 1, nullptr, 0, 0, nullptr, 1, 0, 0, 0) ==
-         hipErrorInvalidValue);  // Kpad small
-  EXPECT(tp_conv_wgrad(n, n, n, n, 2, 8, 8, 64, 64, 3, 1, 1, 576, 7, 1, nullptr, 0, 0, nullptr, 1, 0, 0, 0) ==
-         hipErrorInvalidValue);  // bad cfg
+  // tp_conv_wgrad / tp_wino_wgrad: csrc/tests/wgrad_validation.cpp
   EXPECT(tp_conv_wino(n, nullptr, n, 2, 7, 8, 64, 64, 0, 1, 1, 1, n, n, 0, n, nullptr, n, n, n, n, 0, 0) ==
          hipErrorInvalidValue);  // odd H with 2x2 pooling
   EXPECT(tp_conv_wino(n, nullptr, n, 2, 7, 8, 64, 64, 1, 2, 1, 1, n, n, 0, n, nullptr, n, n, n, n, 0, 0) ==

@@ -208,7 +208,8 @@ def build(verbose: bool = False, force: bool = False, jobs: int | None = None) -
 # program checks, on a CPU-only machine, that the launchers reject unsupported shapes before touching
 # the GPU and that the host-side helpers are memory-clean; no kernel is launched.
 HOST_PROGRAMS = {
-    "launcher_validation": ("wino4", "conv_mfma", "conv_wgrad", "winograd", "batchnorm", "weight_pack"),
+    "launcher_validation": ("wino4", "conv_mfma", "winograd", "batchnorm", "weight_pack"),
+    "wgrad_validation": ("conv_wgrad", "wino_wgrad"),
     "dwconv_validation": ("dwconv",),
     "dwconv_act_validation": ("dwconv_act",),
     "dwconv_hs_validation": ("dwconv_act",),
