@@ -731,12 +731,16 @@ at::Tensor se_bwd_reduce(const at::Tensor& g, const at::Tensor& x) {
   return se_reduce(g, &x);
 }
 
-std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Tensor& w1,
-                                               const c10::optional<at::Tensor>& b1, const at::Tensor& w2,
-                                               const c10::optional<at::Tensor>& b2, int64_t gate) {
+// (h, z1, s): act 0 ReLU (z1 an empty tensor), 1 SiLU (z1 (B, Cs), the pre-activation of h)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_act_fwd(const at::Tensor& p, const at::Tensor& w1,
+                                                               const c10::optional<at::Tensor>& b1,
+                                                               const at::Tensor& w2,
+                                                               const c10::optional<at::Tensor>& b2, int64_t gate,
+                                                               int64_t act) {
   need(p, "p");
   TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && p.numel() > 0, "p must be a non-empty contiguous (B, C) tensor");
   TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
+  TORCH_CHECK(act == 0 || act == 1, "act must be 0 (ReLU) or 1 (SiLU)");
   const int64_t B = p.size(0), C = p.size(1);
   TORCH_CHECK(w1.dim() >= 2, "w1 must be a (Cs, C[, 1, 1]) weight");
   const int64_t Cs = w1.size(0);
@@ -748,24 +752,42 @@ std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Te
   TORCH_CHECK(B * std::max(C, Cs) < (int64_t(1) << 24), "too many rows");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
   auto h = at::empty({B, Cs}, p.options());
+  auto z1 = at::empty({act == 1 ? B : 0, Cs}, p.options());
   auto s = at::empty({B, C}, p.options());
-  TP_CHECK_HIP(tp_se_gate_fwd(p.data_ptr<float>(), w1.data_ptr<float>(), b1p, w2.data_ptr<float>(), b2p,
-                              h.data_ptr<float>(), s.data_ptr<float>(), (int)B, (int)C, (int)Cs, (int)gate,
-                              cur_stream()));
+  TP_CHECK_HIP(tp_se_gate_act_fwd(p.data_ptr<float>(), w1.data_ptr<float>(), b1p, w2.data_ptr<float>(), b2p,
+                                  h.data_ptr<float>(), act == 1 ? z1.data_ptr<float>() : nullptr, s.data_ptr<float>(),
+                                  (int)B, (int)C, (int)Cs, (int)gate, (int)act, cur_stream()));
+  return {h, z1, s};
+}
+
+std::tuple<at::Tensor, at::Tensor> se_gate_fwd(const at::Tensor& p, const at::Tensor& w1,
+                                               const c10::optional<at::Tensor>& b1, const at::Tensor& w2,
+                                               const c10::optional<at::Tensor>& b2, int64_t gate) {
+  auto [h, z1, s] = se_gate_act_fwd(p, w1, b1, w2, b2, gate, 0);
   return {h, s};
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_bwd(const at::Tensor& ds, const at::Tensor& s,
-                                                           const at::Tensor& h, const at::Tensor& w1,
-                                                           const at::Tensor& w2, int64_t gate) {
+// z1: the forward's second output (read for act 1 only)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_act_bwd(const at::Tensor& ds, const at::Tensor& s,
+                                                               const at::Tensor& h,
+                                                               const c10::optional<at::Tensor>& z1,
+                                                               const at::Tensor& w1, const at::Tensor& w2,
+                                                               int64_t gate, int64_t act) {
   need(ds, "ds");
   TORCH_CHECK(ds.dim() == 2 && ds.is_contiguous() && ds.numel() > 0, "ds must be a non-empty contiguous (B, C) tensor");
   TORCH_CHECK(gate == 0 || gate == 1, "gate must be 0 (Hardsigmoid) or 1 (Sigmoid)");
+  TORCH_CHECK(act == 0 || act == 1, "act must be 0 (ReLU) or 1 (SiLU)");
   TORCH_CHECK(h.dim() == 2, "h must be (B, Cs)");
   const int64_t B = ds.size(0), C = ds.size(1), Cs = h.size(1);
   check_se_widths(C, Cs);
   check_se_rows(s, B, C, ds, "s");
   check_se_rows(h, B, Cs, ds, "h");
+  const float* zp = nullptr;
+  if (act == 1) {
+    TORCH_CHECK(z1.has_value() && z1->defined(), "a SiLU gate's backward needs z1");
+    check_se_rows(*z1, B, Cs, ds, "z1");
+    zp = z1->data_ptr<float>();
+  }
   check_se_weight(w1, Cs, C, ds, "w1");
   check_se_weight(w2, C, Cs, ds, "w2");
   TORCH_CHECK(B * std::max(C, Cs) < (int64_t(1) << 24), "too many rows");
@@ -773,10 +795,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_bwd(const at::Tensor& ds,
   auto dz2 = at::empty({B, C}, ds.options());
   auto dz1 = at::empty({B, Cs}, ds.options());
   auto dp = at::empty({B, C}, ds.options());
-  TP_CHECK_HIP(tp_se_gate_bwd(ds.data_ptr<float>(), s.data_ptr<float>(), h.data_ptr<float>(), w1.data_ptr<float>(),
-                              w2.data_ptr<float>(), dz2.data_ptr<float>(), dz1.data_ptr<float>(), dp.data_ptr<float>(),
-                              (int)B, (int)C, (int)Cs, (int)gate, cur_stream()));
+  TP_CHECK_HIP(tp_se_gate_act_bwd(ds.data_ptr<float>(), s.data_ptr<float>(), h.data_ptr<float>(), zp,
+                                  w1.data_ptr<float>(), w2.data_ptr<float>(), dz2.data_ptr<float>(),
+                                  dz1.data_ptr<float>(), dp.data_ptr<float>(), (int)B, (int)C, (int)Cs, (int)gate,
+                                  (int)act, cur_stream()));
   return {dz2, dz1, dp};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> se_gate_bwd(const at::Tensor& ds, const at::Tensor& s,
+                                                           const at::Tensor& h, const at::Tensor& w1,
+                                                           const at::Tensor& w2, int64_t gate) {
+  return se_gate_act_bwd(ds, s, h, c10::nullopt, w1, w2, gate, 0);
 }
 
 at::Tensor se_scale(const at::Tensor& x, const at::Tensor& s) {
@@ -828,6 +857,10 @@ c10::optional<at::Tensor> se_wgrad(const at::Tensor& a, const at::Tensor& m, at:
 TORCH_LIBRARY(tpamd, m) {
   m.def("se_pool(Tensor x) -> Tensor");
   m.def("se_gate_fwd(Tensor p, Tensor w1, Tensor? b1, Tensor w2, Tensor? b2, int gate) -> (Tensor, Tensor)");
+  m.def("se_gate_act_fwd(Tensor p, Tensor w1, Tensor? b1, Tensor w2, Tensor? b2, int gate, int act) "
+        "-> (Tensor h, Tensor z1, Tensor s)");
+  m.def("se_gate_act_bwd(Tensor ds, Tensor s, Tensor h, Tensor? z1, Tensor w1, Tensor w2, int gate, int act) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("se_scale(Tensor x, Tensor s) -> Tensor");
   m.def("se_bwd_reduce(Tensor g, Tensor x) -> Tensor");
   m.def("se_gate_bwd(Tensor ds, Tensor s, Tensor h, Tensor w1, Tensor w2, int gate) -> (Tensor, Tensor, Tensor)");
@@ -891,6 +924,8 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("dwconv_hs_dgrad", &dwconv_hs_dgrad);
   m.impl("se_pool", &se_pool);
   m.impl("se_gate_fwd", &se_gate_fwd);
+  m.impl("se_gate_act_fwd", &se_gate_act_fwd);
+  m.impl("se_gate_act_bwd", &se_gate_act_bwd);
   m.impl("se_scale", &se_scale);
   m.impl("se_bwd_reduce", &se_bwd_reduce);
   m.impl("se_gate_bwd", &se_gate_bwd);

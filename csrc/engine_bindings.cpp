@@ -877,17 +877,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
   return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr), dres};
 }
 
-// y = hardswish(BN(x)), training mode, over the last dim of x (..., C): the statistics, running-stat and
-// ``cr`` semantics of bn_train_fwd, no residual and no mask. Returns (y, mean, invstd, ab) with ab (2, C)
-// the folded affine rows a = gamma * invstd, b = beta - mean * a that bn_hswish_bwd recomputes the
-// pre-activation from.
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_hswish_fwd(
-    const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta, const OptTensor& running_mean,
-    const OptTensor& running_var, double eps, double momentum, const OptTensor& num_batches, int64_t cr) {
+// y = act(BN(x)) with act = Hardswish | SiLU (``launch``: the activation's launcher), training mode,
+// over the last dim of x (..., C): the statistics, running-stat and ``cr`` semantics of bn_train_fwd,
+// no residual and no mask. Returns (y, mean, invstd, ab) with ab (2, C) the folded affine rows
+// a = gamma * invstd, b = beta - mean * a that the backward recomputes the pre-activation from.
+using UnitFwd = decltype(&tp_bn_hswish_fwd_train);
+using UnitBwd = decltype(&tp_bn_hswish_bwd_train);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_unit_fwd(
+    UnitFwd launch, const char* op, const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta,
+    const OptTensor& running_mean, const OptTensor& running_var, double eps, double momentum,
+    const OptTensor& num_batches, int64_t cr) {
   need(x, "x", kAnyDims);
   const int64_t C = x.dim() > 0 ? x.size(-1) : 0, P = x.numel() / std::max<int64_t>(C, 1);
-  TORCH_CHECK(C > 0 && P > 0, "bn_hswish_fwd needs a non-empty batch");
-  TORCH_CHECK(x.numel() < (1ll << 32), "bn_hswish_fwd: 2^32 elements or more");
+  TORCH_CHECK(C > 0 && P > 0, op, " needs a non-empty batch");
+  TORCH_CHECK(x.numel() < (1ll << 32), op, ": 2^32 elements or more");
   const int64_t Cr = cr > 0 ? cr : C;
   TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -902,23 +905,23 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_hswish_fwd(
   auto stats = at::empty({4, Cs}, x.options()).narrow(1, 0, C);  // mean, invstd, a, b
   float* sp = stats.data_ptr<float>();
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
-  TP_CHECK_HIP(tp_bn_hswish_fwd_train(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be,
-                                      (float)eps, (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs,
-                                      ws.data_ptr<double>(), nbt, cur_stream()));
+  TP_CHECK_HIP(launch(x.data_ptr<float>(), y.data_ptr<float>(), (int)P, (int)C, (int)Cr, ga, be, (float)eps,
+                      (float)momentum, rm, rv, sp, sp + Cs, sp + 2 * Cs, sp + 3 * Cs, ws.data_ptr<double>(), nbt,
+                      cur_stream()));
   return {y, stats[0], stats[1], stats.narrow(0, 2, 2)};
 }
 
-// Backward of bn_hswish_fwd: (dx or undefined, dgamma, dbeta). ``ab``: the forward's fourth output.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_hswish_bwd(const at::Tensor& g, const at::Tensor& x,
-                                                             const OptTensor& gamma, const at::Tensor& mean,
-                                                             const at::Tensor& invstd, const at::Tensor& ab,
-                                                             bool want_dx, int64_t cr) {
+// Backward of bn_unit_fwd: (dx or undefined, dgamma, dbeta). ``ab``: the forward's fourth output.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_unit_bwd(UnitBwd launch, const char* op, const at::Tensor& g,
+                                                           const at::Tensor& x, const OptTensor& gamma,
+                                                           const at::Tensor& mean, const at::Tensor& invstd,
+                                                           const at::Tensor& ab, bool want_dx, int64_t cr) {
   need(g, "g", kAnyDims);
   need(x, "x", kAnyDims, &g);
   TORCH_CHECK(g.sizes() == x.sizes(), "g and x must have the same shape");
   const int64_t C = x.dim() > 0 ? x.size(-1) : 0, P = x.numel() / std::max<int64_t>(C, 1);
-  TORCH_CHECK(C > 0 && P > 0, "bn_hswish_bwd needs a non-empty batch");
-  TORCH_CHECK(x.numel() < (1ll << 32), "bn_hswish_bwd: 2^32 elements or more");
+  TORCH_CHECK(C > 0 && P > 0, op, " needs a non-empty batch");
+  TORCH_CHECK(x.numel() < (1ll << 32), op, ": 2^32 elements or more");
   const int64_t Cr = cr > 0 ? cr : C;
   TORCH_CHECK(Cr <= C, "cr must be <= the channel count");
   at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
@@ -932,10 +935,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_hswish_bwd(const at::Tensor& g
   if (want_dx) dx = at::empty_like(x);
   float* cp = coef.data_ptr<float>();
   auto ws = at::empty({2 * (int64_t)tp_bn_groups((int)P, (int)C) * C}, x.options().dtype(at::kDouble));
-  TP_CHECK_HIP(tp_bn_hswish_bwd_train(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dx), (int)P, (int)C,
-                                      (int)Cr, ga, mp, ip, af, bf, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs,
-                                      ws.data_ptr<double>(), cur_stream()));
+  TP_CHECK_HIP(launch(g.data_ptr<float>(), x.data_ptr<float>(), ptr_or_null(dx), (int)P, (int)C, (int)Cr, ga, mp, ip,
+                      af, bf, cp, cp + Cs, cp + 2 * Cs, cp + 3 * Cs, cp + 4 * Cs, ws.data_ptr<double>(),
+                      cur_stream()));
   return {dx, coef[0].narrow(0, 0, Cr), coef[1].narrow(0, 0, Cr)};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_hswish_fwd(
+    const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta, const OptTensor& running_mean,
+    const OptTensor& running_var, double eps, double momentum, const OptTensor& num_batches, int64_t cr) {
+  return bn_unit_fwd(&tp_bn_hswish_fwd_train, "bn_hswish_fwd", x, gamma, beta, running_mean, running_var, eps,
+                     momentum, num_batches, cr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_hswish_bwd(const at::Tensor& g, const at::Tensor& x,
+                                                             const OptTensor& gamma, const at::Tensor& mean,
+                                                             const at::Tensor& invstd, const at::Tensor& ab,
+                                                             bool want_dx, int64_t cr) {
+  return bn_unit_bwd(&tp_bn_hswish_bwd_train, "bn_hswish_bwd", g, x, gamma, mean, invstd, ab, want_dx, cr);
+}
+// y = silu(BN(x)) (EfficientNet's units): the same operands and outputs
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_silu_fwd(
+    const at::Tensor& x, const OptTensor& gamma, const OptTensor& beta, const OptTensor& running_mean,
+    const OptTensor& running_var, double eps, double momentum, const OptTensor& num_batches, int64_t cr) {
+  return bn_unit_fwd(&tp_bn_silu_fwd_train, "bn_silu_fwd", x, gamma, beta, running_mean, running_var, eps, momentum,
+                     num_batches, cr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_silu_bwd(const at::Tensor& g, const at::Tensor& x,
+                                                           const OptTensor& gamma, const at::Tensor& mean,
+                                                           const at::Tensor& invstd, const at::Tensor& ab,
+                                                           bool want_dx, int64_t cr) {
+  return bn_unit_bwd(&tp_bn_silu_bwd_train, "bn_silu_bwd", g, x, gamma, mean, invstd, ab, want_dx, cr);
 }
 
 void register_engine_ops_def(torch::Library& m) {
@@ -964,6 +993,11 @@ void register_engine_ops_def(torch::Library& m) {
         "float eps, float momentum, Tensor(c!)? num_batches=None, int cr=0) "
         "-> (Tensor y, Tensor mean, Tensor invstd, Tensor ab)");
   m.def("bn_hswish_bwd(Tensor g, Tensor x, Tensor? gamma, Tensor mean, Tensor invstd, Tensor ab, bool want_dx, "
+        "int cr=0) -> (Tensor dx, Tensor dgamma, Tensor dbeta)");
+  m.def("bn_silu_fwd(Tensor x, Tensor? gamma, Tensor? beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
+        "float eps, float momentum, Tensor(c!)? num_batches=None, int cr=0) "
+        "-> (Tensor y, Tensor mean, Tensor invstd, Tensor ab)");
+  m.def("bn_silu_bwd(Tensor g, Tensor x, Tensor? gamma, Tensor mean, Tensor invstd, Tensor ab, bool want_dx, "
         "int cr=0) -> (Tensor dx, Tensor dgamma, Tensor dbeta)");
   m.def("conv_wgrad(Tensor g, Tensor x, int ks, int stride, int pad, int cfg, int splits, Tensor(a!)? out=None) "
         "-> Tensor");
@@ -1029,6 +1063,8 @@ void register_engine_ops_impl(torch::Library& m) {
   m.impl("bn_train_bwd", &bn_train_bwd);
   m.impl("bn_hswish_fwd", &bn_hswish_fwd);
   m.impl("bn_hswish_bwd", &bn_hswish_bwd);
+  m.impl("bn_silu_fwd", &bn_silu_fwd);
+  m.impl("bn_silu_bwd", &bn_silu_bwd);
   m.impl("unpool2_nhwc", &unpool2_nhwc);
   m.impl("conv_wino_dgrad", &conv_wino_dgrad);
   m.impl("wino4_weights", &wino4_weights);

@@ -111,6 +111,14 @@ struct FastDiv {
   __device__ __forceinline__ int div(int n) const { return (int)((__umulhi((unsigned)n, m) + (unsigned)n) >> l); }
 };
 
+// A kernel compiled without packed fp32 VALU ops (v_pk_fma_f32 and kin): the float4 lanes of an
+// elementwise kernel stay scalar fmas. Per kernel, so the kernels beside it are compiled as before.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TP_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define TP_NO_PK_F32
+#endif
+
 inline unsigned ceil_div(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace tp

@@ -33,6 +33,14 @@ hipError_t tp_bn_hswish_bwd_train(const float* g, const float* x, float* dx, int
                                   const float* mean, const float* invstd, const float* af, const float* bf,
                                   float* dgamma, float* dbeta, float* a, float* k1, float* k2, double* ws,
                                   hipStream_t st);
+// y = silu(BN(x)) and its backward: the Hardswish tail's argument lists and checks
+hipError_t tp_bn_silu_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma, const float* beta,
+                                float eps, float momentum, float* run_mean, float* run_var, float* mean,
+                                float* invstd, float* a, float* b, double* ws, long long* nbt, hipStream_t st);
+hipError_t tp_bn_silu_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr, const float* gamma,
+                                const float* mean, const float* invstd, const float* af, const float* bf,
+                                float* dgamma, float* dbeta, float* a, float* k1, float* k2, double* ws,
+                                hipStream_t st);
 // channel_reduce.hip
 hipError_t tp_channel_reduce(const float* act, const float* grad, float* out, float* ws, int B, int C, int S,
                              int mode, int channels_last, hipStream_t st);
@@ -157,6 +165,13 @@ hipError_t tp_se_bwd_reduce(const float* g, const float* x, float* ds, float* ws
                             hipStream_t st);
 hipError_t tp_se_gate_bwd(const float* ds, const float* s, const float* h, const float* w1, const float* w2,
                           float* dz2, float* dz1, float* dp, int B, int C, int Cs, int gate, hipStream_t st);
+// the gate with an inner activation code act: 0 ReLU (z1 unused, may be null), 1 SiLU (z1 (B, Cs): the
+// pre-activation of h, written by the forward and read by the backward)
+hipError_t tp_se_gate_act_fwd(const float* p, const float* w1, const float* b1, const float* w2, const float* b2,
+                              float* h, float* z1, float* s, int B, int C, int Cs, int gate, int act, hipStream_t st);
+hipError_t tp_se_gate_act_bwd(const float* ds, const float* s, const float* h, const float* z1, const float* w1,
+                              const float* w2, float* dz2, float* dz1, float* dp, int B, int C, int Cs, int gate,
+                              int act, hipStream_t st);
 hipError_t tp_se_bwd_dx(const float* g, const float* s, const float* dp, float* dx, int B, int HW, int C,
                         hipStream_t st);
 hipError_t tp_se_wgrad(const float* a, const float* m, float* dw, float* db, int B, int R, int K, long long s0,

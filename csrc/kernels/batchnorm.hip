@@ -15,6 +15,8 @@
 //
 // A block owns a 64-wide column quad range (16 threads x float4) x 16 row lanes, and walks
 // rows_per_group rows; the 16 row lanes are folded in LDS in a fixed order.
+#include <type_traits>
+
 #include "tp_common.h"
 #include "tp_launchers.h"
 
@@ -409,15 +411,39 @@ __device__ __forceinline__ float hswish_bwd(float g, float v) {
   if (v <= 3.f) return g * (v / 3.f + 0.5f);
   return g;
 }
-__device__ __forceinline__ float4 hswish_bwd4(float4 g, float4 x, float4 a, float4 b) {
-  return make_float4(hswish_bwd(g.x, bn_pre(x.x, a.x, b.x)), hswish_bwd(g.y, bn_pre(x.y, a.y, b.y)),
-                     hswish_bwd(g.z, bn_pre(x.z, a.z, b.z)), hswish_bwd(g.w, bn_pre(x.w, a.w, b.w)));
+// ---- BN + SiLU (EfficientNet units): y = v * s, s = sigmoid(v), same contract as the Hardswish tail ---
+// s = 1 / (1 + exp(-v)), one exponential and one reciprocal per element and pass, shared by the value
+// and the derivative s * (1 + v * (1 - s)). This form saturates cleanly: exp(-v) overflows to +inf
+// for v << 0 (s = 0: y = -0, derivative 0) and underflows to 0 for v >> 0 (s = 1: y = v, derivative
+// 1), where exp(v) / (1 + exp(v)) would give inf / inf. A NaN v gives NaN in y and in gm (ATen's
+// silu / silu_backward). A padding channel (a = b = 0) gives v = 0 and y = 0.
+// The exponential is the library expf: with the hardware one (__expf) the whole backward measured 4 %
+// faster, within the spread of the runs (profiles/silu/silu_kernel_stats.txt).
+__device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
+
+// The activation of a fused unit tail: value and gradient factor at the pre-activation v
+struct ActHswish {
+  static __device__ __forceinline__ float fwd(float v) { return hswish(v); }
+  static __device__ __forceinline__ float bwd(float g, float v) { return hswish_bwd(g, v); }
+};
+struct ActSilu {
+  static __device__ __forceinline__ float fwd(float v) { return v * sigmoidf(v); }
+  static __device__ __forceinline__ float bwd(float g, float v) {
+    const float s = sigmoidf(v);
+    return g * (s * (1.f + v * (1.f - s)));
+  }
+};
+template <typename ACT>
+__device__ __forceinline__ float4 act_bwd4(float4 g, float4 x, float4 a, float4 b) {
+  return make_float4(ACT::bwd(g.x, bn_pre(x.x, a.x, b.x)), ACT::bwd(g.y, bn_pre(x.y, a.y, b.y)),
+                     ACT::bwd(g.z, bn_pre(x.z, a.z, b.z)), ACT::bwd(g.w, bn_pre(x.w, a.w, b.w)));
 }
 
-// Backward statistics (sum gm, sum gm * xhat) with gm = g * hswish'(x * af + bf), per row group into
+// Backward statistics (sum gm, sum gm * xhat) with gm = g * act'(x * af + bf), per row group into
 // the [groups][2][C] workspace of bn_partial<1> (same block shape, same row walk, same fold order).
-template <bool V4>
-__global__ __launch_bounds__(BN_T) void bn_hswish_partial(const float* __restrict__ x, const float* __restrict__ g,
+// The bodies are shared by the two activations' kernels below.
+template <typename ACT, bool V4>
+__device__ __forceinline__ void act_partial_body(const float* __restrict__ x, const float* __restrict__ g,
                                                           const float* __restrict__ mean,
                                                           const float* __restrict__ invstd,
                                                           const float* __restrict__ af, const float* __restrict__ bf,
@@ -442,7 +468,7 @@ __global__ __launch_bounds__(BN_T) void bn_hswish_partial(const float* __restric
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const float4 m = hswish_bwd4(d[u], v[u], av, bv);
+        const float4 m = act_bwd4<ACT>(d[u], v[u], av, bv);
         s0.x += m.x;
         s0.y += m.y;
         s0.z += m.z;
@@ -455,7 +481,7 @@ __global__ __launch_bounds__(BN_T) void bn_hswish_partial(const float* __restric
     }
     for (; r < r1; r += BN_RL) {
       const float4 v = ld4<V4>(x, (size_t)r * C, c, C);
-      const float4 m = hswish_bwd4(ld4<V4>(g, (size_t)r * C, c, C), v, av, bv);
+      const float4 m = act_bwd4<ACT>(ld4<V4>(g, (size_t)r * C, c, C), v, av, bv);
       s0.x += m.x;
       s0.y += m.y;
       s0.z += m.z;
@@ -485,11 +511,11 @@ __global__ __launch_bounds__(BN_T) void bn_hswish_partial(const float* __restric
   }
 }
 
-// forward (BWD = false): out = hswish(x * a + b)
-// backward (BWD = true): out = gm * a + k1 + k2 * x, gm = g * hswish'(x * af + bf); channels c >= Cr
+// forward (BWD = false): out = act(x * a + b), act = ACT (ActHswish | ActSilu)
+// backward (BWD = true): out = gm * a + k1 + k2 * x, gm = g * act'(x * af + bf); channels c >= Cr
 // (padding) get an exact 0 whatever g holds there
-template <bool BWD>
-__global__ __launch_bounds__(256) void bn_hswish_apply(const float* __restrict__ x, const float* __restrict__ g,
+template <typename ACT, bool BWD>
+__device__ __forceinline__ void unit_apply_body(const float* __restrict__ x, const float* __restrict__ g,
                                                        const float* __restrict__ af, const float* __restrict__ bf,
                                                        const float* __restrict__ a, const float* __restrict__ k1,
                                                        const float* __restrict__ k2, float* __restrict__ out,
@@ -501,7 +527,7 @@ __global__ __launch_bounds__(256) void bn_hswish_apply(const float* __restrict__
     const float4 fb = *reinterpret_cast<const float4*>(bf + c);
     float4 o;
     if (BWD) {
-      const float4 m = hswish_bwd4(reinterpret_cast<const float4*>(g)[t], v, fa, fb);
+      const float4 m = act_bwd4<ACT>(reinterpret_cast<const float4*>(g)[t], v, fa, fb);
       const float4 av = *reinterpret_cast<const float4*>(a + c);
       const float4 bv = *reinterpret_cast<const float4*>(k1 + c);
       const float4 kv = *reinterpret_cast<const float4*>(k2 + c);
@@ -510,19 +536,19 @@ __global__ __launch_bounds__(256) void bn_hswish_apply(const float* __restrict__
       o.z = c + 2 < Cr ? m.z * av.z + bv.z + kv.z * v.z : 0.f;
       o.w = c + 3 < Cr ? m.w * av.w + bv.w + kv.w * v.w : 0.f;
     } else {
-      o.x = hswish(bn_pre(v.x, fa.x, fb.x));
-      o.y = hswish(bn_pre(v.y, fa.y, fb.y));
-      o.z = hswish(bn_pre(v.z, fa.z, fb.z));
-      o.w = hswish(bn_pre(v.w, fa.w, fb.w));
+      o.x = ACT::fwd(bn_pre(v.x, fa.x, fb.x));
+      o.y = ACT::fwd(bn_pre(v.y, fa.y, fb.y));
+      o.z = ACT::fwd(bn_pre(v.z, fa.z, fb.z));
+      o.w = ACT::fwd(bn_pre(v.w, fa.w, fb.w));
     }
     reinterpret_cast<float4*>(out)[t] = o;
   }
 }
 
-// bn_hswish_apply for C % 4 != 0: thread t owns flat elements 4t..4t+3 (< n), each with its own
+// unit_apply_body for C % 4 != 0: thread t owns flat elements 4t..4t+3 (< n), each with its own
 // channel (e % C), per-element loads and stores
-template <bool BWD>
-__global__ __launch_bounds__(256) void bn_hswish_apply_any(const float* __restrict__ x, const float* __restrict__ g,
+template <typename ACT, bool BWD>
+__device__ __forceinline__ void unit_apply_any_body(const float* __restrict__ x, const float* __restrict__ g,
                                                            const float* __restrict__ af, const float* __restrict__ bf,
                                                            const float* __restrict__ a, const float* __restrict__ k1,
                                                            const float* __restrict__ k2, float* __restrict__ out,
@@ -535,10 +561,47 @@ __global__ __launch_bounds__(256) void bn_hswish_apply_any(const float* __restri
       if (e >= n) break;
       const unsigned c = (unsigned)(e % C);
       const float xv = x[e], v = bn_pre(xv, af[c], bf[c]);
-      if (BWD) out[e] = c < Cr ? hswish_bwd(g[e], v) * a[c] + k1[c] + k2[c] * xv : 0.f;
-      else out[e] = hswish(v);
+      if (BWD) out[e] = c < Cr ? ACT::bwd(g[e], v) * a[c] + k1[c] + k2[c] * xv : 0.f;
+      else out[e] = ACT::fwd(v);
     }
   }
+}
+
+#define TP_UNIT_PARTIAL_ARGS                                                                                       \
+  const float *__restrict__ x, const float *__restrict__ g, const float *__restrict__ mean,                       \
+      const float *__restrict__ invstd, const float *__restrict__ af, const float *__restrict__ bf,               \
+      double *__restrict__ part, int P, int C, int rows_per_group
+#define TP_UNIT_APPLY_ARGS(N_T, C_T)                                                                              \
+  const float *__restrict__ x, const float *__restrict__ g, const float *__restrict__ af,                         \
+      const float *__restrict__ bf, const float *__restrict__ a, const float *__restrict__ k1,                    \
+      const float *__restrict__ k2, float *__restrict__ out, N_T n, C_T C, unsigned Cr
+
+// Hardswish: the kernels as they were before the bodies were shared
+template <bool V4>
+__global__ __launch_bounds__(BN_T) void bn_hswish_partial(TP_UNIT_PARTIAL_ARGS) {
+  act_partial_body<ActHswish, V4>(x, g, mean, invstd, af, bf, part, P, C, rows_per_group);
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_hswish_apply(TP_UNIT_APPLY_ARGS(unsigned, unsigned)) {
+  unit_apply_body<ActHswish, BWD>(x, g, af, bf, a, k1, k2, out, n, C, Cr);
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_hswish_apply_any(TP_UNIT_APPLY_ARGS(unsigned long long, unsigned)) {
+  unit_apply_any_body<ActHswish, BWD>(x, g, af, bf, a, k1, k2, out, n, C, Cr);
+}
+// SiLU: compiled without packed fp32 ops (89 VGPRs and 5 waves per SIMD in the statistics kernel
+// instead of 100 and 4)
+template <bool V4>
+__global__ __launch_bounds__(BN_T) TP_NO_PK_F32 void bn_silu_partial(TP_UNIT_PARTIAL_ARGS) {
+  act_partial_body<ActSilu, V4>(x, g, mean, invstd, af, bf, part, P, C, rows_per_group);
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) TP_NO_PK_F32 void bn_silu_apply(TP_UNIT_APPLY_ARGS(unsigned, unsigned)) {
+  unit_apply_body<ActSilu, BWD>(x, g, af, bf, a, k1, k2, out, n, C, Cr);
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) TP_NO_PK_F32 void bn_silu_apply_any(TP_UNIT_APPLY_ARGS(unsigned long long, unsigned)) {
+  unit_apply_any_body<ActSilu, BWD>(x, g, af, bf, a, k1, k2, out, n, C, Cr);
 }
 
 inline int bn_groups(int P, int C) {
@@ -661,32 +724,39 @@ extern "C" hipError_t tp_bn_bwd_train_pre(const float* g, const float* x, float*
 }
 
 namespace tp {
-// launch bn_hswish_apply (float4 rows) or bn_hswish_apply_any (per-element) over the (P, C) activation
-template <bool BWD>
-static void hswish_apply_launch(const float* x, const float* g, const float* af, const float* bf, const float* a,
-                                const float* k1, const float* k2, float* out, long long P, int C, int Cr,
-                                hipStream_t st) {
+// launch the activation's apply kernel (float4 rows, or per-element for C % 4 != 0) over the (P, C) activation
+template <typename ACT, bool BWD>
+static void unit_apply_launch(const float* x, const float* g, const float* af, const float* bf, const float* a,
+                              const float* k1, const float* k2, float* out, long long P, int C, int Cr,
+                              hipStream_t st) {
   const long long n = P * C;
   if (C % 4 == 0) {
     const unsigned n4 = (unsigned)(n / 4);
-    bn_hswish_apply<BWD><<<(unsigned)std::min<long long>(ceil_div((long long)n4, 256), 8192), 256, 0, st>>>(
-        x, g, af, bf, a, k1, k2, out, n4, (unsigned)(C / 4), (unsigned)Cr);
+    const unsigned blocks = (unsigned)std::min<long long>(ceil_div((long long)n4, 256), 8192);
+    if constexpr (std::is_same_v<ACT, ActSilu>)
+      bn_silu_apply<BWD><<<blocks, 256, 0, st>>>(x, g, af, bf, a, k1, k2, out, n4, (unsigned)(C / 4), (unsigned)Cr);
+    else
+      bn_hswish_apply<BWD><<<blocks, 256, 0, st>>>(x, g, af, bf, a, k1, k2, out, n4, (unsigned)(C / 4), (unsigned)Cr);
   } else {
     const long long n4 = (n + 3) / 4;
-    bn_hswish_apply_any<BWD><<<(unsigned)std::min<long long>(ceil_div(n4, 256), 8192), 256, 0, st>>>(
-        x, g, af, bf, a, k1, k2, out, (unsigned long long)n, (unsigned)C, (unsigned)Cr);
+    const unsigned blocks = (unsigned)std::min<long long>(ceil_div(n4, 256), 8192);
+    if constexpr (std::is_same_v<ACT, ActSilu>)
+      bn_silu_apply_any<BWD><<<blocks, 256, 0, st>>>(x, g, af, bf, a, k1, k2, out, (unsigned long long)n, (unsigned)C,
+                                                     (unsigned)Cr);
+    else
+      bn_hswish_apply_any<BWD><<<blocks, 256, 0, st>>>(x, g, af, bf, a, k1, k2, out, (unsigned long long)n,
+                                                       (unsigned)C, (unsigned)Cr);
   }
 }
-}  // namespace tp
 
-// Fused unit tail y = hardswish(BN(x)) (MobileNetV3's Conv-BN-Hardswish units): the statistics pass
-// and the finalize of tp_bn_fwd_train (same running statistics, nbt, mean / invstd / a / b), then one
-// apply pass. No residual, no mask: the backward recomputes the pre-activation from x and (a, b).
-extern "C" hipError_t tp_bn_hswish_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
-                                             const float* beta, float eps, float momentum, float* run_mean,
-                                             float* run_var, float* mean, float* invstd, float* a, float* b,
-                                             double* ws, long long* nbt, hipStream_t st) {
-  using namespace tp;
+// Fused unit tail y = act(BN(x)): the statistics pass and the finalize of tp_bn_fwd_train (same running
+// statistics, nbt, mean / invstd / a / b), then one apply pass. No residual, no mask: the backward
+// recomputes the pre-activation from x and (a, b).
+template <typename ACT>
+static hipError_t unit_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                 const float* beta, float eps, float momentum, float* run_mean, float* run_var,
+                                 float* mean, float* invstd, float* a, float* b, double* ws, long long* nbt,
+                                 hipStream_t st) {
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
   const int groups = bn_groups(P, C);
   const int rpg = (P + groups - 1) / groups;
@@ -694,27 +764,68 @@ extern "C" hipError_t tp_bn_hswish_fwd_train(const float* x, float* y, int P, in
   partial_launch<0>(grid, x, nullptr, nullptr, nullptr, ws, P, C, rpg, nullptr, nullptr, st);
   bn_fwd_finalize<<<(C + 15) / 16, BN_FIN_T, 0, st>>>(ws, groups, P, C, Cr, gamma, beta, eps, momentum, run_mean,
                                                     run_var, mean, invstd, a, b, nbt, bn_fold_lanes());
-  hswish_apply_launch<false>(x, nullptr, a, b, nullptr, nullptr, nullptr, y, P, C, Cr, st);
+  unit_apply_launch<ACT, false>(x, nullptr, a, b, nullptr, nullptr, nullptr, y, P, C, Cr, st);
   return hipGetLastError();
 }
 
 // Its backward. af / bf: the forward's a / b as it wrote them (the pre-activation is recomputed from
 // them, not from gamma / mean / invstd). dx nullable (dgamma / dbeta only). Channels c >= Cr: padding
 // (dx = 0 there, no dgamma / dbeta written). ws as tp_bn_bwd_train.
-extern "C" hipError_t tp_bn_hswish_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
-                                             const float* gamma, const float* mean, const float* invstd,
-                                             const float* af, const float* bf, float* dgamma, float* dbeta, float* a,
-                                             float* k1, float* k2, double* ws, hipStream_t st) {
-  using namespace tp;
+template <typename ACT>
+static hipError_t unit_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr, const float* gamma,
+                                 const float* mean, const float* invstd, const float* af, const float* bf,
+                                 float* dgamma, float* dbeta, float* a, float* k1, float* k2, double* ws,
+                                 hipStream_t st) {
   if (C <= 0 || P <= 0 || Cr <= 0 || Cr > C || (long long)P * C >= (1ll << 32)) return hipErrorInvalidValue;
   if (!af || !bf) return hipErrorInvalidValue;
   const int groups = bn_groups(P, C);
   const int rpg = (P + groups - 1) / groups;
   const dim3 grid((C + BN_CQ * 4 - 1) / (BN_CQ * 4), groups);
-  if (C % 4 == 0) bn_hswish_partial<true><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
-  else bn_hswish_partial<false><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+  if constexpr (std::is_same_v<ACT, ActSilu>) {
+    if (C % 4 == 0) bn_silu_partial<true><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+    else bn_silu_partial<false><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+  } else {
+    if (C % 4 == 0) bn_hswish_partial<true><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+    else bn_hswish_partial<false><<<grid, BN_T, 0, st>>>(x, g, mean, invstd, af, bf, ws, P, C, rpg);
+  }
   bn_bwd_finalize<<<(C + 15) / 16, BN_FIN_T, 0, st>>>(ws, groups, P, C, Cr, gamma, mean, invstd, dgamma, dbeta, a, k1,
                                                       k2, bn_fold_lanes());
-  if (dx) hswish_apply_launch<true>(x, g, af, bf, a, k1, k2, dx, P, C, Cr, st);
+  if (dx) unit_apply_launch<ACT, true>(x, g, af, bf, a, k1, k2, dx, P, C, Cr, st);
   return hipGetLastError();
+}
+
+}  // namespace tp
+
+// y = hardswish(BN(x)) (MobileNetV3's Conv-BN-Hardswish units) and its backward
+extern "C" hipError_t tp_bn_hswish_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                             const float* beta, float eps, float momentum, float* run_mean,
+                                             float* run_var, float* mean, float* invstd, float* a, float* b,
+                                             double* ws, long long* nbt, hipStream_t st) {
+  return tp::unit_fwd_train<tp::ActHswish>(x, y, P, C, Cr, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd,
+                                           a, b, ws, nbt, st);
+}
+
+extern "C" hipError_t tp_bn_hswish_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
+                                             const float* gamma, const float* mean, const float* invstd,
+                                             const float* af, const float* bf, float* dgamma, float* dbeta, float* a,
+                                             float* k1, float* k2, double* ws, hipStream_t st) {
+  return tp::unit_bwd_train<tp::ActHswish>(g, x, dx, P, C, Cr, gamma, mean, invstd, af, bf, dgamma, dbeta, a, k1, k2,
+                                           ws, st);
+}
+
+// y = silu(BN(x)) (EfficientNet's Conv-BN-SiLU units) and its backward: the same argument lists
+extern "C" hipError_t tp_bn_silu_fwd_train(const float* x, float* y, int P, int C, int Cr, const float* gamma,
+                                           const float* beta, float eps, float momentum, float* run_mean,
+                                           float* run_var, float* mean, float* invstd, float* a, float* b, double* ws,
+                                           long long* nbt, hipStream_t st) {
+  return tp::unit_fwd_train<tp::ActSilu>(x, y, P, C, Cr, gamma, beta, eps, momentum, run_mean, run_var, mean, invstd,
+                                         a, b, ws, nbt, st);
+}
+
+extern "C" hipError_t tp_bn_silu_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
+                                           const float* gamma, const float* mean, const float* invstd, const float* af,
+                                           const float* bf, float* dgamma, float* dbeta, float* a, float* k1, float* k2,
+                                           double* ws, hipStream_t st) {
+  return tp::unit_bwd_train<tp::ActSilu>(g, x, dx, P, C, Cr, gamma, mean, invstd, af, bf, dgamma, dbeta, a, k1, k2, ws,
+                                         st);
 }

@@ -1,5 +1,6 @@
 // Squeeze-and-excitation gates (MobileNetV3 / EfficientNet) of the training path, fp32 NHWC:
-//   out = x * s,  s = gate(W2 . relu(W1 . mean_hw(x) + b1) + b2),  gate = Hardsigmoid | Sigmoid
+//   out = x * s,  s = gate(W2 . act(W1 . mean_hw(x) + b1) + b2),  gate = Hardsigmoid | Sigmoid,
+//   act = ReLU (MobileNetV3) | SiLU (EfficientNet)
 // x is (B, H, W, C) at its real width. ANY channel count is taken (pruned widths are arbitrary): a
 // float4 path when C % 4 == 0 and a per-element path otherwise, as dwconv.hip. The passes over
 // the activation are memory-bound and are the only ones that matter: forward reads x twice (pool,
@@ -174,15 +175,24 @@ __device__ __forceinline__ void se_rows_dot(const float* __restrict__ w, const f
   }
 }
 
-// One block per image: h = relu(W1 . p + b1) (Cs), s = gate(W2 . h + b2) (C), the rows of both
-// weights by se_rows_dot.
-__global__ __launch_bounds__(SE_FC_THREADS) void se_gate_fwd_k(const float* __restrict__ p,
-                                                               const float* __restrict__ w1,
-                                                               const float* __restrict__ b1,
-                                                               const float* __restrict__ w2,
-                                                               const float* __restrict__ b2, float* __restrict__ h,
-                                                               float* __restrict__ s, int C, int Cs, int g1, int g2,
-                                                               int gate) {
+// The inner activation of a gate (ACT 0 ReLU, 1 SiLU) at z1 = W1 . p + b1, and its derivative. SiLU as
+// in batchnorm.hip: s = 1 / (1 + exp(-z)) saturates to 0 / 1 without an inf / inf, NaN passes through.
+constexpr int SE_ACT_RELU = 0, SE_ACT_SILU = 1;
+__device__ __forceinline__ float se_silu(float z) { return z / (1.f + expf(-z)); }
+__device__ __forceinline__ float se_silu_grad(float z) {
+  const float s = 1.f / (1.f + expf(-z));
+  return s * (1.f + z * (1.f - s));
+}
+
+// One block per image: h = act(z1) (Cs), z1 = W1 . p + b1, s = gate(W2 . h + b2) (C), the rows of both
+// weights by se_rows_dot. SiLU also stores z1: its derivative cannot be read from h (silu is not
+// monotonic, h does not determine z1).
+template <int ACT>
+__device__ __forceinline__ void se_gate_fwd_body(const float* __restrict__ p, const float* __restrict__ w1,
+                                                 const float* __restrict__ b1, const float* __restrict__ w2,
+                                                 const float* __restrict__ b2, float* __restrict__ h,
+                                                 float* __restrict__ z1, float* __restrict__ s, int C, int Cs, int g1,
+                                                 int g2, int gate) {
   extern __shared__ float lds[];
   float* pl = lds;      // C
   float* hl = lds + C;  // Cs
@@ -190,7 +200,14 @@ __global__ __launch_bounds__(SE_FC_THREADS) void se_gate_fwd_k(const float* __re
   for (int c = threadIdx.x; c < C; c += SE_FC_THREADS) pl[c] = p[b * C + c];
   __syncthreads();
   se_rows_dot(w1, pl, Cs, C, g1, [&](int j, float acc) {
-    const float v = nan_relu(acc + (b1 != nullptr ? b1[j] : 0.f));
+    const float z = acc + (b1 != nullptr ? b1[j] : 0.f);
+    float v;
+    if constexpr (ACT == SE_ACT_SILU) {
+      z1[b * Cs + j] = z;
+      v = se_silu(z);
+    } else {
+      v = nan_relu(z);
+    }
     hl[j] = v;
     h[b * Cs + j] = v;
   });
@@ -199,13 +216,15 @@ __global__ __launch_bounds__(SE_FC_THREADS) void se_gate_fwd_k(const float* __re
               [&](int c, float acc) { s[b * C + c] = se_gate(acc + (b2 != nullptr ? b2[c] : 0.f), gate); });
 }
 
-// One block per image: dz2 = ds * gate'(s) (C), dz1 = (dz2 . W2) * [h > 0] (Cs), dp = dz1 . W1 (C).
+// One block per image: dz2 = ds * gate'(s) (C), dz1 = (dz2 . W2) * act' (Cs), dp = dz1 . W1 (C); act' is
+// [h > 0] for ReLU (hz = h) and silu'(z1) for SiLU (hz = z1).
 // Both products run down the columns of a row-major weight: a thread owns a column (consecutive
 // lanes read consecutive addresses); for dz1 the rows are dealt to `parts` = threads / tj threads
 // per column, whose partial sums are folded in part order through the LDS.
-__global__ __launch_bounds__(SE_FC_THREADS) void se_gate_bwd_k(const float* __restrict__ ds,
+template <int ACT>
+__device__ __forceinline__ void se_gate_bwd_body(const float* __restrict__ ds,
                                                                const float* __restrict__ s,
-                                                               const float* __restrict__ h,
+                                                               const float* __restrict__ hz,
                                                                const float* __restrict__ w1,
                                                                const float* __restrict__ w2, float* __restrict__ dz2,
                                                                float* __restrict__ dz1, float* __restrict__ dp, int C,
@@ -236,7 +255,9 @@ __global__ __launch_bounds__(SE_FC_THREADS) void se_gate_bwd_k(const float* __re
     if (pt == 0 && j < Cs) {
       float t = 0.f;
       for (int i = 0; i < parts; ++i) t += part[i * tj + jl];
-      const float v = h[b * Cs + j] > 0.f ? t : 0.f;
+      float v;
+      if constexpr (ACT == SE_ACT_SILU) v = t * se_silu_grad(hz[b * Cs + j]);
+      else v = hz[b * Cs + j] > 0.f ? t : 0.f;
       z1[j] = v;
       dz1[b * Cs + j] = v;
     }
@@ -248,6 +269,39 @@ __global__ __launch_bounds__(SE_FC_THREADS) void se_gate_bwd_k(const float* __re
     for (int j = 0; j < Cs; ++j) acc = fmaf(z1[j], w1[j * C + c], acc);
     dp[b * C + c] = acc;
   }
+}
+
+// The ReLU gate's kernels as they were before the bodies were shared, and the SiLU gate's (compiled
+// without packed fp32 ops)
+__global__ __launch_bounds__(SE_FC_THREADS) void se_gate_fwd_k(const float* __restrict__ p,
+                                                               const float* __restrict__ w1,
+                                                               const float* __restrict__ b1,
+                                                               const float* __restrict__ w2,
+                                                               const float* __restrict__ b2, float* __restrict__ h,
+                                                               float* __restrict__ s, int C, int Cs, int g1, int g2,
+                                                               int gate) {
+  se_gate_fwd_body<SE_ACT_RELU>(p, w1, b1, w2, b2, h, nullptr, s, C, Cs, g1, g2, gate);
+}
+__global__ __launch_bounds__(SE_FC_THREADS) TP_NO_PK_F32 void se_gate_fwd_silu_k(
+    const float* __restrict__ p, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ h, float* __restrict__ z1,
+    float* __restrict__ s, int C, int Cs, int g1, int g2, int gate) {
+  se_gate_fwd_body<SE_ACT_SILU>(p, w1, b1, w2, b2, h, z1, s, C, Cs, g1, g2, gate);
+}
+__global__ __launch_bounds__(SE_FC_THREADS) void se_gate_bwd_k(const float* __restrict__ ds,
+                                                               const float* __restrict__ s,
+                                                               const float* __restrict__ h,
+                                                               const float* __restrict__ w1,
+                                                               const float* __restrict__ w2, float* __restrict__ dz2,
+                                                               float* __restrict__ dz1, float* __restrict__ dp, int C,
+                                                               int Cs, int tj, int gate) {
+  se_gate_bwd_body<SE_ACT_RELU>(ds, s, h, w1, w2, dz2, dz1, dp, C, Cs, tj, gate);
+}
+__global__ __launch_bounds__(SE_FC_THREADS) TP_NO_PK_F32 void se_gate_bwd_silu_k(
+    const float* __restrict__ ds, const float* __restrict__ s, const float* __restrict__ z1,
+    const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ dz2, float* __restrict__ dz1,
+    float* __restrict__ dp, int C, int Cs, int tj, int gate) {
+  se_gate_bwd_body<SE_ACT_SILU>(ds, s, z1, w1, w2, dz2, dz1, dp, C, Cs, tj, gate);
 }
 
 // dW[r, k] = sum_b a[b, r] * m[b, k] at dw[r * s0 + k * s1] (the parameter's strides) and, with db,
@@ -359,32 +413,57 @@ extern "C" hipError_t tp_se_bwd_reduce(const float* g, const float* x, float* ds
   return se_reduce(g, x, ds, ws, splits, B, HW, C, true, 1.0, st);
 }
 
-// h (B, Cs) = relu(p . W1^T + b1), s (B, C) = gate(h . W2^T + b2); w1 (Cs, C), w2 (C, Cs) row-major,
-// b1 / b2 may be null; gate 0 Hardsigmoid, 1 Sigmoid
-extern "C" hipError_t tp_se_gate_fwd(const float* p, const float* w1, const float* b1, const float* w2,
-                                     const float* b2, float* h, float* s, int B, int C, int Cs, int gate,
-                                     hipStream_t st) {
+// h (B, Cs) = act(z1), z1 = p . W1^T + b1, s (B, C) = gate(h . W2^T + b2); w1 (Cs, C), w2 (C, Cs)
+// row-major, b1 / b2 may be null; gate 0 Hardsigmoid, 1 Sigmoid; act 0 ReLU, 1 SiLU (stores z1 (B, Cs))
+extern "C" hipError_t tp_se_gate_act_fwd(const float* p, const float* w1, const float* b1, const float* w2,
+                                         const float* b2, float* h, float* z1, float* s, int B, int C, int Cs,
+                                         int gate, int act, hipStream_t st) {
   if (p == nullptr || w1 == nullptr || w2 == nullptr || h == nullptr || s == nullptr) return hipErrorInvalidValue;
-  if ((gate != 0 && gate != 1) || !tp::se_fc_ok(B, C, Cs)) return hipErrorInvalidValue;
-  if (!tp::se_aligned(1, p, w1, w2, h) || !tp::se_aligned(1, s, b1, b2)) return hipErrorInvalidValue;
+  if ((gate != 0 && gate != 1) || (act != tp::SE_ACT_RELU && act != tp::SE_ACT_SILU) || !tp::se_fc_ok(B, C, Cs))
+    return hipErrorInvalidValue;
+  if (act == tp::SE_ACT_SILU && z1 == nullptr) return hipErrorInvalidValue;
+  if (!tp::se_aligned(1, p, w1, w2, h) || !tp::se_aligned(1, s, b1, b2, z1)) return hipErrorInvalidValue;
   const int g1 = tp::se_pow2_at_least(C, 64), g2 = tp::se_pow2_at_least(Cs, 64);
-  tp::se_gate_fwd_k<<<B, tp::SE_FC_THREADS, (size_t)(C + Cs) * sizeof(float), st>>>(p, w1, b1, w2, b2, h, s, C, Cs, g1, g2, gate);
+  const size_t lds = (size_t)(C + Cs) * sizeof(float);
+  if (act == tp::SE_ACT_SILU)
+    tp::se_gate_fwd_silu_k<<<B, tp::SE_FC_THREADS, lds, st>>>(p, w1, b1, w2, b2, h, z1, s, C, Cs, g1, g2, gate);
+  else
+    tp::se_gate_fwd_k<<<B, tp::SE_FC_THREADS, lds, st>>>(p, w1, b1, w2, b2, h, s, C, Cs, g1, g2, gate);
   return hipGetLastError();
 }
 
-// dz2 (B, C) = ds * gate'(s), dz1 (B, Cs) = (dz2 . W2) * [h > 0], dp (B, C) = dz1 . W1
-extern "C" hipError_t tp_se_gate_bwd(const float* ds, const float* s, const float* h, const float* w1,
-                                     const float* w2, float* dz2, float* dz1, float* dp, int B, int C, int Cs,
-                                     int gate, hipStream_t st) {
+extern "C" hipError_t tp_se_gate_fwd(const float* p, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, float* h, float* s, int B, int C, int Cs, int gate,
+                                     hipStream_t st) {
+  return tp_se_gate_act_fwd(p, w1, b1, w2, b2, h, nullptr, s, B, C, Cs, gate, tp::SE_ACT_RELU, st);
+}
+
+// dz2 (B, C) = ds * gate'(s), dz1 (B, Cs) = (dz2 . W2) * act', dp (B, C) = dz1 . W1; act' = [h > 0] for
+// ReLU (z1 unused), silu'(z1) for SiLU
+extern "C" hipError_t tp_se_gate_act_bwd(const float* ds, const float* s, const float* h, const float* z1,
+                                         const float* w1, const float* w2, float* dz2, float* dz1, float* dp, int B,
+                                         int C, int Cs, int gate, int act, hipStream_t st) {
   if (ds == nullptr || s == nullptr || h == nullptr || w1 == nullptr || w2 == nullptr || dz2 == nullptr ||
       dz1 == nullptr || dp == nullptr)
     return hipErrorInvalidValue;
-  if ((gate != 0 && gate != 1) || !tp::se_fc_ok(B, C, Cs)) return hipErrorInvalidValue;
-  if (!tp::se_aligned(1, ds, s, h, w1) || !tp::se_aligned(1, w2, dz2, dz1, dp)) return hipErrorInvalidValue;
+  if ((gate != 0 && gate != 1) || (act != tp::SE_ACT_RELU && act != tp::SE_ACT_SILU) || !tp::se_fc_ok(B, C, Cs))
+    return hipErrorInvalidValue;
+  if (act == tp::SE_ACT_SILU && z1 == nullptr) return hipErrorInvalidValue;
+  if (!tp::se_aligned(1, ds, s, h, w1) || !tp::se_aligned(1, w2, dz2, dz1, dp) || !tp::se_aligned(1, z1, z1))
+    return hipErrorInvalidValue;
   const int tj = tp::se_pow2_at_least(Cs, tp::SE_FC_THREADS);
-  tp::se_gate_bwd_k<<<B, tp::SE_FC_THREADS, (size_t)(C + Cs + tp::SE_FC_THREADS) * sizeof(float), st>>>(
-      ds, s, h, w1, w2, dz2, dz1, dp, C, Cs, tj, gate);
+  const size_t lds = (size_t)(C + Cs + tp::SE_FC_THREADS) * sizeof(float);
+  if (act == tp::SE_ACT_SILU)
+    tp::se_gate_bwd_silu_k<<<B, tp::SE_FC_THREADS, lds, st>>>(ds, s, z1, w1, w2, dz2, dz1, dp, C, Cs, tj, gate);
+  else
+    tp::se_gate_bwd_k<<<B, tp::SE_FC_THREADS, lds, st>>>(ds, s, h, w1, w2, dz2, dz1, dp, C, Cs, tj, gate);
   return hipGetLastError();
+}
+
+extern "C" hipError_t tp_se_gate_bwd(const float* ds, const float* s, const float* h, const float* w1,
+                                     const float* w2, float* dz2, float* dz1, float* dp, int B, int C, int Cs,
+                                     int gate, hipStream_t st) {
+  return tp_se_gate_act_bwd(ds, s, h, nullptr, w1, w2, dz2, dz1, dp, B, C, Cs, gate, tp::SE_ACT_RELU, st);
 }
 
 // shared body of the scale and the input gradient: out = a * s[b, c] (+ dp[b, c] / HW)

@@ -30,7 +30,9 @@ one launch each way. A ``(BatchNorm2d, Hardswish)`` pair of a plain ``nn.Sequent
 expand and depthwise units of the Hardswish blocks, the last conv) runs as one fused tail
 (:func:`bn_hswish`: statistics, then one apply pass; the backward recomputes the pre-activation from
 x and the forward's folded affine, nothing but x is kept); ``TORCHPRUNER_FUSE_HSWISH=0`` keeps the
-native BN followed by ATen's hardswish. The classifier's ``Linear -> Hardswish`` stays an ATen op.
+native BN followed by ATen's hardswish. The classifier's ``Linear -> Hardswish`` stays an ATen op. EfficientNet's
+``(BatchNorm2d, SiLU)`` pairs fuse the same way (:func:`bn_silu`, ``TORCHPRUNER_FUSE_SILU=0`` for the
+A/B), and its gates, whose inner activation is a SiLU, run on the same three launches.
 
 Training-mode ``BatchNorm2d`` runs on deterministic NHWC batch-statistics / normalisation /
 backward kernels (K5, ``tpamd.bn_train_*``), training-mode ``nn.Dropout`` on a counter-based
@@ -181,19 +183,23 @@ _BWD_FUSE = os.environ.get("TORCHPRUNER_BN_BWD_FUSE", "1") != "0"
 _MB_FUSE = os.environ.get("TORCHPRUNER_FUSE_RELU6", "1") != "0"
 # passes that took each fusion (tests / diagnostics). Backward: tail statistics from a dgrad epilogue,
 # identity gradients handed over unmasked. Forward: fused BN + ReLU6 tails, inverted-residual blocks
-# on the fused block forward, depthwise convs on a carried (padded) width, fused BN + Hardswish tails
+# on the fused block forward, depthwise convs on a carried (padded) width, fused BN + Hardswish and
+# BN + SiLU tails
 FUSE_COUNTS = {"bn_stats_from_dgrad": 0, "raw_residual": 0, "bn_relu6": 0, "ir_block": 0, "dw_carried": 0,
-               "bn_hswish": 0}
+               "bn_hswish": 0, "bn_silu": 0}
 # TORCHPRUNER_FUSE_HSWISH=0: (BatchNorm2d, Hardswish) pairs of an nn.Sequential stay unfused (the native
 # BN, then ATen's hardswish on the real-width slice); A/B switch, consulted at every Sequential forward
 _HS_FUSE = os.environ.get("TORCHPRUNER_FUSE_HSWISH", "1") != "0"
+# TORCHPRUNER_FUSE_SILU=0: the same switch for (BatchNorm2d, SiLU) pairs (EfficientNet units)
+_SILU_FUSE = os.environ.get("TORCHPRUNER_FUSE_SILU", "1") != "0"
 # TORCHPRUNER_NATIVE_DW=0: depthwise convs stay on the library path (A/B switch, read once)
 _NATIVE_DW = os.environ.get("TORCHPRUNER_NATIVE_DW", "1") != "0"
 # launches of the depthwise kernels (tests / diagnostics)
 DW_COUNTS = {"fwd": 0, "dgrad": 0, "wgrad": 0}
 # TORCHPRUNER_NATIVE_SE=0: squeeze-and-excitation gates stay on the library path (A/B switch, read once)
 _NATIVE_SE = os.environ.get("TORCHPRUNER_NATIVE_SE", "1") != "0"
-# gate forwards / backwards that ran on the squeeze_excite kernels (tests / diagnostics)
+# gate forwards / backwards that ran on the squeeze_excite kernels, ReLU and SiLU gates alike (tests /
+# diagnostics)
 SE_COUNTS = {"fwd": 0, "bwd": 0}
 
 
@@ -867,6 +873,52 @@ def bn_hswish(bn: nn.BatchNorm2d, x: torch.Tensor) -> torch.Tensor:
                                  nbt, bn.num_features)
 
 
+class _NativeBNSiLU(torch.autograd.Function):
+    """Fused training-mode unit tail ``silu(BN(x))`` (EfficientNet), the contract of
+    :class:`_NativeBNHswish`: x and the folded affine rows ``ab`` are all the backward keeps (autograd's
+    own SiLU saves the whole pre-activation), and ATen's silu / silu_backward passes disappear."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, nbt=None, cr=0):
+        xh = _nhwc(x)
+        w = weight.detach() if weight is not None else None
+        b = bias.detach() if bias is not None else None
+        y, mean, invstd, ab = ops.require().bn_silu_fwd(xh, w, b, running_mean, running_var, float(eps),
+                                                        float(momentum), nbt, int(cr))
+        FUSE_COUNTS["bn_silu"] += 1
+        ctx.cr = int(cr)
+        if running_mean is not None:
+            epochs.bump_stats()  # running stats written by the kernel: no version bump
+        ctx.save_for_backward(xh, w if w is not None else torch.empty(0, device=x.device), mean, invstd, ab)
+        ctx.has_w, ctx.has_b = weight is not None, bias is not None
+        return _as_nchw(y)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xh, w, mean, invstd, ab = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.require().bn_silu_bwd(_nhwc(gy), xh, w if ctx.has_w else None, mean, invstd, ab,
+                                                      ctx.needs_input_grad[0], ctx.cr)
+        return (_as_nchw(dx) if ctx.needs_input_grad[0] else None, dgamma if ctx.has_w else None,
+                dbeta if ctx.has_b else None, None, None, None, None, None, None)
+
+
+def bn_silu(bn: nn.BatchNorm2d, x: torch.Tensor) -> torch.Tensor:
+    """``silu(bn(x))`` — fused on the native kernels in training mode (fp32 GPU input at the module's
+    width, or a padded activation carrying more: it stays padded, silu(0) = 0), the module's own ops
+    otherwise (eval mode, unsupported inputs)."""
+    if not _bn_fusable(bn, x):
+        return F.silu(bn(_real(x, bn.num_features)))
+    momentum, nbt = bn.momentum, _bn_counter(bn)
+    if nbt is None and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if momentum is None:
+            momentum = 1.0 / float(bn.num_batches_tracked)
+    rm = bn.running_mean if bn.track_running_stats else None
+    rv = bn.running_var if bn.track_running_stats else None
+    return _NativeBNSiLU.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, momentum if momentum is not None else 0.0,
+                               nbt, bn.num_features)
+
+
 def _block_kind(m) -> str | None:
     """torchvision-layout residual blocks whose training forward can use the fused tails."""
     names = ("conv1", "bn1", "conv2", "bn2", "relu", "downsample")
@@ -946,7 +998,9 @@ def _sequential_forward(self, x, mb):
     ReLU6) pairs fuse too, ReLU6 passes a padded activation on, and a native depthwise conv takes
     the padded activation and keeps it padded. With or without ``mb``, a (BatchNorm2d, Hardswish)
     pair runs as one :func:`bn_hswish` tail and passes a padded activation on padded, unless
-    :data:`_HS_FUSE` is off (read here, at call time) or one of the two modules has a hook."""
+    :data:`_HS_FUSE` is off (read here, at call time) or one of the two modules has a hook; a
+    (BatchNorm2d, SiLU) pair runs as one :func:`bn_silu` tail under the same conditions
+    (:data:`_SILU_FUSE`)."""
     mods = list(self.children())
     real = None  # real channel count while x is a padded activation
     i = 0
@@ -960,6 +1014,11 @@ def _sequential_forward(self, x, mb):
         if _HS_FUSE and isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and type(mods[i + 1]) is nn.Hardswish \
                 and _bn_fusable(m, x) and not _any_hooked((m, mods[i + 1])):
             x = bn_hswish(m, x)  # a padded activation stays padded: hardswish(0) = 0
+            i += 2
+            continue
+        if _SILU_FUSE and isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and type(mods[i + 1]) is nn.SiLU \
+                and _bn_fusable(m, x) and not _any_hooked((m, mods[i + 1])):
+            x = bn_silu(m, x)  # a padded activation stays padded: silu(0) = 0
             i += 2
             continue
         if "forward" in m.__dict__ and getattr(m.forward, "__func__", None) is _native_forward \
@@ -1165,7 +1224,8 @@ def _native_dw_forward(self, x):
 
 
 class _NativeSE(torch.autograd.Function):
-    """Squeeze-and-excitation gate ``x * gate(fc2(relu(fc1(mean_hw(x)))))`` on the NHWC kernels of
+    """Squeeze-and-excitation gate ``x * gate(fc2(act(fc1(mean_hw(x)))))``, act = ReLU | SiLU (``act`` 0 |
+    1; a SiLU gate also keeps fc1's output z1, which its derivative is read from), on the NHWC kernels of
     ``squeeze_excite.hip``: forward is a pool pass, one launch for both FCs and a scale pass;
     backward one product-reduce pass over (g, x), one launch for the FC chain and one pass that
     writes ``dx = g * s + dp / HW`` (the pool's broadcast gradient and the scale's gradient never
@@ -1174,26 +1234,32 @@ class _NativeSE(torch.autograd.Function):
     in the parameters' shapes and strides, and are skipped for frozen parameters."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gate):
+    def forward(ctx, x, w1, b1, w2, b2, gate, act=0):
         T = ops.require()
         xh = _nhwc(x)  # no copy for a channels_last input
         w1c, w2c = w1.detach().contiguous(), w2.detach().contiguous()
         p = T.se_pool(xh)
-        h, s = T.se_gate_fwd(p, w1c, b1.detach() if b1 is not None else None, w2c,
-                             b2.detach() if b2 is not None else None, gate)
+        b1d, b2d = (b.detach() if b is not None else None for b in (b1, b2))
+        if act:
+            h, z1, s = T.se_gate_act_fwd(p, w1c, b1d, w2c, b2d, gate, act)
+        else:
+            (h, s), z1 = T.se_gate_fwd(p, w1c, b1d, w2c, b2d, gate), None
         out = T.se_scale(xh, s)
         SE_COUNTS["fwd"] += 1
-        ctx.save_for_backward(xh, p, h, s, w1c, w2c)
-        ctx.meta = (gate, w1.stride(), w2.stride(), b1 is not None, b2 is not None)
+        ctx.save_for_backward(xh, p, h, s, w1c, w2c, *(() if z1 is None else (z1,)))
+        ctx.meta = (gate, w1.stride(), w2.stride(), b1 is not None, b2 is not None, act)
         return _as_nchw(out)
 
     @staticmethod
     def backward(ctx, gy):
         T = ops.require()
-        xh, p, h, s, w1c, w2c = ctx.saved_tensors
-        gate, st1, st2, has_b1, has_b2 = ctx.meta
+        xh, p, h, s, w1c, w2c, *z1 = ctx.saved_tensors
+        gate, st1, st2, has_b1, has_b2, act = ctx.meta
         g = _nhwc(gy)
-        dz2, dz1, dp = T.se_gate_bwd(T.se_bwd_reduce(g, xh), s, h, w1c, w2c, gate)
+        if act:
+            dz2, dz1, dp = T.se_gate_act_bwd(T.se_bwd_reduce(g, xh), s, h, z1[0], w1c, w2c, gate, act)
+        else:
+            dz2, dz1, dp = T.se_gate_bwd(T.se_bwd_reduce(g, xh), s, h, w1c, w2c, gate)
         SE_COUNTS["bwd"] += 1
         dx = _as_nchw(T.se_bwd_dx(g, s, dp)) if ctx.needs_input_grad[0] else None
         grads = []
@@ -1209,27 +1275,40 @@ class _NativeSE(torch.autograd.Function):
                 if not need_w:
                     dw = None
             grads += [dw, db]
-        return (dx, *grads, None)
+        return (dx, *grads, None, None)
+
+
+def _se_codes(m) -> tuple[int, int] | None:
+    """The kernels' (gate, inner activation) codes of a channel gate with torchvision's
+    ``SqueezeExcitation`` children (a global ``avgpool``, a ReLU / SiLU ``activation``, a Hardsigmoid /
+    Sigmoid ``scale_activation``), else None."""
+    pool, act, gate = (getattr(m, n, None) for n in ("avgpool", "activation", "scale_activation"))
+    if not (type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1), [1, 1])):
+        return None
+    inner = {nn.ReLU: 0, nn.SiLU: 1}.get(type(act))  # ops.se.SE_ACTS
+    code = 0 if type(gate) is nn.Hardsigmoid else 1 if type(gate) is nn.Sigmoid else None
+    return None if inner is None or code is None else (code, inner)
 
 
 def _se_gate_code(m) -> int | None:
-    """The kernels' gate code of a channel gate with torchvision's ``SqueezeExcitation`` children (a
-    global ``avgpool``, a ReLU ``activation``, a Hardsigmoid / Sigmoid ``scale_activation``), else None."""
-    pool, act, gate = (getattr(m, n, None) for n in ("avgpool", "activation", "scale_activation"))
-    if not (type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1), [1, 1]) and type(act) is nn.ReLU):
-        return None
-    return 0 if type(gate) is nn.Hardsigmoid else 1 if type(gate) is nn.Sigmoid else None
+    """The gate code of a ReLU gate (the gates the MobileNet attribution engine lowers), else None."""
+    codes = _se_codes(m)
+    return codes[0] if codes is not None and codes[1] == 0 else None
 
 
-def se_eligible(m: nn.Module) -> bool:
+def se_eligible(m: nn.Module, silu: bool = False) -> bool:
     """Channel gates (``utils.graph.is_channel_gate``) the native kernels compute: a global average
-    pool, fc1, ReLU, fc2 and a Hardsigmoid or Sigmoid gate (other inner activations, SiLU for one,
-    stay on the module's forward). Caveat: the test reads the children (torchvision's
+    pool, fc1, ReLU, fc2 and a Hardsigmoid or Sigmoid gate; with ``silu`` (what
+    :func:`enable_native_convs` asks) also EfficientNet's gates, whose inner activation is a SiLU
+    (the training path computes them, the MobileNet attribution engine does not lower them; any
+    other inner activation stays on the module's forward). So the default answer for a SiLU gate is
+    False although :func:`enable_native_convs` switches it: a test of the earlier behaviour pins
+    ``se_eligible(gate)`` for such a gate. Caveat: the test reads the children (torchvision's
     ``SqueezeExcitation`` names and types), not the module's ``forward``; a module with exactly
     these children that computes something else from them (a residual gate, a second use of the
     pooled tensor) would be computed as ``x * s`` all the same. Exclude such a module by calling
     :func:`disable_native_convs` on it, or with ``TORCHPRUNER_NATIVE_SE=0``."""
-    return is_channel_gate(m) and _se_gate_code(m) is not None
+    return is_channel_gate(m) and (_se_codes(m) if silu else _se_gate_code(m)) is not None
 
 
 def _se_fits(x: torch.Tensor, C: int, Cs: int) -> bool:
@@ -1244,15 +1323,15 @@ def _native_se_forward(self, x):
     called then, so the gate takes its own forward whenever one of them has a hook or global module
     hooks exist, as for other dtypes / devices, tensors beyond 2 GiB and a gate whose structure
     changed since it was switched; a hook on the gate module itself still fires."""
-    gate = _se_gate_code(self) if is_channel_gate(self) else None
-    if gate is None or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+    codes = _se_codes(self) if is_channel_gate(self) else None
+    if codes is None or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
         return type(self).forward(self, x)
     fc1, fc2 = self.fc1, self.fc2
     (Cs, C), params = fc1.weight.shape[:2], (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
     if x.shape[1] != C or fc2.weight.shape[1] != Cs or not _se_fits(x, C, Cs) or _hooked(self) \
             or any(t is not None and (t.dtype != torch.float32 or t.device != x.device) for t in params):
         return type(self).forward(self, x)
-    return _NativeSE.apply(x, *params, gate)
+    return _NativeSE.apply(x, *params, *codes)
 
 
 def _ir_unit(u) -> bool:
@@ -1438,9 +1517,10 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
     ``nn.Sequential`` (MobileNetV3 units) run as one fused tail in training mode (:func:`bn_hswish`;
     neither module is called then), except when one of the two has a forward / backward hook or
     global module hooks exist: the pair then runs its modules; ``TORCHPRUNER_FUSE_HSWISH=0`` turns
-    this fusion off. Also switched: depthwise convs
+    this fusion off. ``(BatchNorm2d, SiLU)`` pairs (EfficientNet units) fuse the same way
+    (:func:`bn_silu`; ``TORCHPRUNER_FUSE_SILU=0``). Also switched: depthwise convs
     (:func:`dw_eligible`, the NHWC stencil kernels; ``TORCHPRUNER_NATIVE_DW=0`` leaves them on the
-    library path), squeeze-and-excitation gates (:func:`se_eligible`, train and eval mode, with or
+    library path), squeeze-and-excitation gates (:func:`se_eligible`, SiLU gates included; train and eval mode, with or
     without ``fuse``: pool, both FCs, gate and scale on the ``squeeze_excite`` kernels; the modules
     inside the gate are not called then, so a gate with a hook on one of them takes its own forward,
     while a hook on the gate itself still fires; ``TORCHPRUNER_NATIVE_SE=0`` leaves gates on the
@@ -1465,7 +1545,7 @@ def enable_native_convs(model: nn.Module, bn: bool = True, fuse: bool = True, dr
             m.forward = types.MethodType(_native_ir_forward, m)
             switched.append(m)
             inner.update(id(c) for c in m.conv.modules() if type(c) is nn.Sequential)
-        elif _NATIVE_SE and se_eligible(m):
+        elif _NATIVE_SE and se_eligible(m, silu=True):
             # (its pool and fcs are switched further down like any other leaf: the gate's fallback
             # forward still runs them on the native kernels)
             m.forward = types.MethodType(_native_se_forward, m)

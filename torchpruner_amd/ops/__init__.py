@@ -12,9 +12,11 @@ import torch
 
 from ._native import available, backend, load, require, use_native
 from .bn_hswish import bn_hswish_bwd, bn_hswish_fwd
+from .bn_silu import bn_silu_bwd, bn_silu_fwd
 from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 from .dwconv_hs import dwconv_hs_dgrad, dwconv_hs_fwd, dwconv_hs_tay_slots
-from .se import SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_bwd, se_gate_fwd, se_pool, se_scale, se_wgrad
+from .se import (SE_ACTS, SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_act_bwd, se_gate_act_fwd, se_gate_bwd,
+                 se_gate_fwd, se_pool, se_scale, se_wgrad)
 
 __all__ = [
     "available", "backend", "load", "require", "use_native",
@@ -23,7 +25,8 @@ __all__ = [
     "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
     "dwconv_hs_fwd", "dwconv_hs_dgrad", "dwconv_hs_tay_slots",
     "SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad",
-    "bn_hswish_fwd", "bn_hswish_bwd",
+    "SE_ACTS", "se_gate_act_fwd", "se_gate_act_bwd",
+    "bn_hswish_fwd", "bn_hswish_bwd", "bn_silu_fwd", "bn_silu_bwd",
 ]
 
 REDUCE_MODES = {"taylor": 0, "taylor_signed": 1, "sensitivity": 2, "apoz": 3, "sum_grad": 4}

@@ -10,6 +10,11 @@
               db = se_wgrad(a, m, dw, want_bias)     dw[r, k] = sum_b a[b, r] m[b, k], db[r] = sum_b a[b, r]
                                                      (dW2: a = dz2, m = h; dW1: a = dz1, m = p)
 
+``se_gate_act_fwd`` / ``se_gate_act_bwd`` are the same two steps with an inner activation code ``act``:
+0 (ReLU, as above) or 1 (SiLU, EfficientNet's gates): h = silu(z1) with z1 = p w1^T + b1, which the
+forward also returns (SiLU's derivative s (1 + z1 (1 - s)), s = sigmoid(z1), cannot be read from h),
+and dz1 = (dz2 w2) * silu'(z1).
+
 ``gate`` is 0 (Hardsigmoid: clamp(z + 3, 0, 6) / 6, derivative 1/6 where 0 < s < 1) or 1 (Sigmoid,
 derivative s (1 - s)): both derivatives are read from the stored s, the ReLU's from the stored h.
 The weights are taken in the parameters' own layout: ``(Cs, C)`` of an ``nn.Linear`` or
@@ -24,9 +29,11 @@ import torch
 
 from ._native import require, use_native
 
-__all__ = ["SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad"]
+__all__ = ["SE_GATES", "SE_ACTS", "se_pool", "se_gate_fwd", "se_gate_act_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd",
+           "se_gate_act_bwd", "se_bwd_dx", "se_wgrad"]
 
 SE_GATES = {"hardsigmoid": 0, "sigmoid": 1}
+SE_ACTS = {"relu": 0, "silu": 1}
 SE_MAX_FC = 12288  # C + Cs of the gate kernels (their rows live in the LDS)
 
 
@@ -44,6 +51,12 @@ def _check_gate(gate: int) -> int:
     if gate not in (0, 1):
         raise ValueError(f"gate code {gate}: 0 (Hardsigmoid) or 1 (Sigmoid)")
     return int(gate)
+
+
+def _check_inner(act: int) -> int:
+    if act not in (0, 1):
+        raise ValueError(f"inner activation code {act}: 0 (ReLU) or 1 (SiLU)")
+    return int(act)
 
 
 def _fc(w: torch.Tensor, n_out: int, n_in: int, name: str) -> torch.Tensor:
@@ -88,6 +101,61 @@ def se_gate_fwd(p: torch.Tensor, w1: torch.Tensor, b1, w2: torch.Tensor, b2, gat
         z2 = z2 + b2.to(p.dtype)
     s = torch.clamp(z2 + 3.0, 0.0, 6.0) / 6.0 if gate == 0 else torch.sigmoid(z2)
     return h, s
+
+
+def se_gate_act_fwd(p: torch.Tensor, w1: torch.Tensor, b1, w2: torch.Tensor, b2, gate: int = 1, act: int = 1):
+    """p (B, C) -> (h (B, Cs), z1 (B, Cs) or an empty tensor for ``act`` 0, s (B, C))."""
+    gate, act = _check_gate(gate), _check_inner(act)
+    if p.dim() != 2 or p.numel() == 0 or w1.dim() < 2:
+        raise ValueError("p must be a non-empty (B, C) tensor and w1 a (Cs, C[, 1, 1]) weight")
+    (B, C), Cs = p.shape, w1.shape[0]
+    m1, m2 = _fc(w1, Cs, C, "w1"), _fc(w2, C, Cs, "w2")
+    for b, n, name in ((b1, Cs, "b1"), (b2, C, "b2")):
+        if b is not None and tuple(b.shape) != (n,):
+            raise ValueError(f"{name} must be ({n},), got {tuple(b.shape)}")
+    if C + Cs > SE_MAX_FC:
+        raise ValueError(f"gate widths C + Cs = {C + Cs} exceed {SE_MAX_FC}")
+    if use_native(p):
+        return tuple(require().se_gate_act_fwd(_c(p), _c(w1), _c(b1), _c(w2), _c(b2), gate, act))
+    z1 = p @ m1.t().to(p.dtype)
+    if b1 is not None:
+        z1 = z1 + b1.to(p.dtype)
+    h = z1 * torch.sigmoid(z1) if act == 1 else torch.clamp(z1, min=0.0)
+    z2 = h @ m2.t().to(p.dtype)
+    if b2 is not None:
+        z2 = z2 + b2.to(p.dtype)
+    s = torch.clamp(z2 + 3.0, 0.0, 6.0) / 6.0 if gate == 0 else torch.sigmoid(z2)
+    return h, (z1 if act == 1 else z1.new_empty(0, Cs)), s
+
+
+def se_gate_act_bwd(ds: torch.Tensor, s: torch.Tensor, h: torch.Tensor, z1, w1: torch.Tensor, w2: torch.Tensor,
+                    gate: int = 1, act: int = 1):
+    """ds, s (B, C), h (B, Cs), z1 (B, Cs; read for ``act`` 1 only) -> (dz2 (B, C), dz1 (B, Cs), dp (B, C))."""
+    gate, act = _check_gate(gate), _check_inner(act)
+    if ds.dim() != 2 or ds.numel() == 0 or h.dim() != 2:
+        raise ValueError("ds must be a non-empty (B, C) tensor and h (B, Cs)")
+    (B, C), Cs = ds.shape, h.shape[1]
+    _check_rows(s, B, C, "s")
+    _check_rows(h, B, Cs, "h")
+    if act == 1:
+        if z1 is None:
+            raise ValueError("a SiLU gate's backward needs z1")
+        _check_rows(z1, B, Cs, "z1")
+    m1, m2 = _fc(w1, Cs, C, "w1"), _fc(w2, C, Cs, "w2")
+    if C + Cs > SE_MAX_FC:
+        raise ValueError(f"gate widths C + Cs = {C + Cs} exceed {SE_MAX_FC}")
+    if use_native(ds):
+        return tuple(require().se_gate_act_bwd(_c(ds), _c(s), _c(h), _c(z1) if act == 1 else None, _c(w1), _c(w2),
+                                               gate, act))
+    d = ((s > 0) & (s < 1)).to(ds.dtype) / 6.0 if gate == 0 else s * (1.0 - s)
+    dz2 = ds * d
+    if act == 1:
+        sg = torch.sigmoid(z1)
+        slope = sg * (1.0 + z1 * (1.0 - sg))
+    else:
+        slope = (h > 0).to(ds.dtype)
+    dz1 = (dz2 @ m2.to(ds.dtype)) * slope
+    return dz2, dz1, dz1 @ m1.to(ds.dtype)
 
 
 def se_scale(x: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
