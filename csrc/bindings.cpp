@@ -248,6 +248,45 @@ at::Tensor prefix_project(const at::Tensor& base, const at::Tensor& a, const at:
   return out;
 }
 
+// out[j, n, :] = (a[n, :] * sc[j, n / hw, :]) @ wt + bias[j, n / hw, :] (+ res[n, :]): the cnt stacked outputs of a
+// 1x1 project conv whose input copies are one activation under per-(copy, image, channel) scales
+// (csrc/kernels/scaled_project.hip)
+at::Tensor scaled_project(const at::Tensor& a, const at::Tensor& sc, const at::Tensor& wt, const at::Tensor& bias,
+                          const OptTensor& res, int64_t hw) {
+  need(a, "a", 2);
+  need(sc, "sc", 3, &a);
+  need(wt, "wt", 2, &a);
+  need(bias, "bias", 3, &a);
+  const int64_t N = a.size(0), C = a.size(1), cnt = sc.size(0), B = sc.size(1), Co = wt.size(1);
+  TORCH_CHECK(N > 0 && C > 0 && Co > 0 && cnt > 0 && B > 0, "scaled_project: empty operand");
+  TORCH_CHECK(hw >= 1 && N % hw == 0 && B * hw == N, "scaled_project: a has ", N, " rows, sc ", B, " images of hw ", hw);
+  TORCH_CHECK(sc.size(2) == C && wt.size(0) == C, "sc must be (cnt, B, ", C, ") and wt (", C, ", Co)");
+  TORCH_CHECK(bias.size(0) == cnt && bias.size(1) == B && bias.size(2) == Co, "bias must be (", cnt, ", ", B, ", ", Co,
+              "), got ", bias.sizes());
+  TORCH_CHECK(C % 4 == 0 && Co % 4 == 0, "scaled_project needs C % 4 == 0 and Co % 4 == 0");
+  const float* rp = nullptr;
+  if (present(res)) {
+    need(*res, "res", 2, &a);
+    TORCH_CHECK(res->size(0) == N && res->size(1) == Co, "res must be (", N, ", ", Co, "), got ", res->sizes());
+    need_aligned16(*res, "res");
+    rp = res->data_ptr<float>();
+  }
+  need_aligned16(a, "a");
+  need_aligned16(sc, "sc");
+  need_aligned16(wt, "wt");
+  need_aligned16(bias, "bias");
+  const int64_t lim = int64_t(1) << 29;  // floats of 2^31 bytes
+  TORCH_CHECK(N < lim && C < lim && Co < lim && cnt < lim && N * C < lim && C * Co < lim && N * Co < lim &&
+                  N * Co * cnt < lim && B * std::max(C, Co) * cnt < lim,
+              "scaled_project operands must stay below 2^31 bytes");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  auto out = at::empty({cnt, N, Co}, a.options());
+  TP_CHECK_HIP(tp_scaled_project(a.data_ptr<float>(), sc.data_ptr<float>(), wt.data_ptr<float>(),
+                                 bias.data_ptr<float>(), rp, out.data_ptr<float>(), (int)N, (int)C, (int)Co, (int)B,
+                                 (int)hw, (int)cnt, cur_stream()));
+  return out;
+}
+
 void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv, int64_t row0, int64_t k0,
                      double scale) {
   need(L, "losses");
@@ -874,6 +913,7 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("gather_multi(Tensor[] srcs, int[] axes, Tensor keep) -> Tensor[]");
   m.def("prefix_mask(Tensor z, Tensor rank, int p0, int K) -> Tensor");
   m.def("prefix_project(Tensor base, Tensor a, Tensor fill, Tensor wt, Tensor perm, int p0, int cnt) -> Tensor");
+  m.def("scaled_project(Tensor a, Tensor sc, Tensor wt, Tensor bias, Tensor? res, int hw) -> Tensor");
   m.def("shapley_scatter(Tensor L, Tensor perm, Tensor(a!) sv, int row0, int k0, float scale) -> ()");
   m.def("shapley_column(Tensor L, Tensor perm, Tensor(a!) sv_col, int k0, float scale) -> ()");
   m.def("cross_entropy(Tensor logits, Tensor target, float gscale, bool want_grad) -> (Tensor, Tensor)");
@@ -907,6 +947,7 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("gather_multi", &gather_multi);
   m.impl("prefix_mask", &prefix_mask);
   m.impl("prefix_project", &prefix_project);
+  m.impl("scaled_project", &scaled_project);
   m.impl("shapley_scatter", &shapley_scatter);
   m.impl("shapley_column", &shapley_column);
   m.impl("cross_entropy", &cross_entropy);

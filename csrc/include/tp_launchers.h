@@ -130,6 +130,11 @@ hipError_t tp_dwconv_hs_dgrad(const float* g, const float* y, const float* w, co
 // (base (N, Co), a (N, C), fill (C), wt (C, Co), perm (n <= C), out (cnt, N, Co); Co % 4 == 0)
 hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt, const int* perm,
                              float* out, int N, int C, int Co, int n, int p0, int cnt, hipStream_t st);
+// scaled_project.hip: out[j, n, :] = (a[n, :] * sc[j, n / HW, :]) @ wt + bias[j, n / HW, :] (+ res[n, :])
+// (a (N, C), sc (cnt, B, C), wt (C, Co), bias (cnt, B, Co), res (N, Co) or null, out (cnt, N, Co); N = B * HW,
+// C % 4 == 0, Co % 4 == 0, every operand 16-byte aligned)
+hipError_t tp_scaled_project(const float* a, const float* sc, const float* wt, const float* bias, const float* res,
+                             float* out, int N, int C, int Co, int B, int HW, int cnt, hipStream_t st);
 // prune_ops.hip
 hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx, int nidx, float value,
                            hipStream_t st);

@@ -357,14 +357,16 @@ class ShapleyAttributionMetric(_AttributionMetric):
         return prepare
 
     def _mobilenet_prepare(self, module, why=None):
-        """Prefix evaluation on the MobileNet engine (opt-in; the ReLU6 after a block's expand or
+        """Prefix evaluation on the MobileNet engine (opt-in; the activation after a block's expand or
         depthwise conv, any loss): the block's input and post-depthwise output are produced once per
         batch; the K stacked outputs of the block's linear project conv come from one conv of the
-        base prefix and a running rank-1 subtraction per pixel (``ops.prefix_project``; the K masked
-        copies of the 6x wider hidden activation are never built), and go through the rest of the
-        network in ONE engine forward."""
+        base prefix and a running rank-1 subtraction per pixel (``ops.prefix_project``), or behind a
+        MobileNetV3 gate from the channel-scaled project GEMM (``ops.scaled_project``: per-copy
+        scales and biases of the one hidden activation). Either way the K masked copies of the 4-6x
+        wider hidden activation are never built, and the outputs go through the rest of the network
+        in ONE engine forward."""
         from ...engine.fused_chain import engine_criterion, per_sample_loss
-        eng = self._mobilenet_engine([module], why, shapley=True)  # None for a MobileNetV3: no prefix scan behind a gate
+        eng = self._mobilenet_engine([module], why, shapley=True)  # V2 and V3 layouts
         if eng is None:
             return None
         crit = engine_criterion(self.criterion, self.device)  # None: the fused cross-entropy kernel

@@ -32,8 +32,9 @@ time: no two-stream pipeline, no graph replay. fp32 throughout.
 
 MobileNetV3 nets (``build_mobilenet_v3_plan`` / ``MobileNetV3Engine``, second half of this file) run
 the same way with ReLU / Hardswish units (``tpamd.dwconv_hs_*``), the squeeze-and-excitation gate
-between the depthwise output and the project conv, and a two-layer classifier; Shapley is not
-served there.
+between the depthwise output and the project conv, and a two-layer classifier; the Shapley prefixes
+of a gated block are per-(copy, image, channel) scales and biases of ONE hidden activation
+(``ops.scaled_project``, csrc/kernels/scaled_project.hip).
 """
 from __future__ import annotations
 
@@ -392,7 +393,7 @@ class MobileNetEngine(ResNetEngine):
                 return bi, "dw"
             if b.expand is not None and module is b.expand.act:
                 return bi, "expand"
-        raise KeyError("not a block ReLU6 of this MobileNet")
+        raise KeyError("not a block activation (after an expand or depthwise conv) of this MobileNet")
 
     def forward_to(self, x: torch.Tensor, bi: int):
         """(block ``bi``'s input h, its post-depthwise ReLU6 output y), both in engine layout: the
@@ -504,12 +505,12 @@ class MobileNetEngine(ResNetEngine):
 # cannot be read from the output), a squeeze-and-excitation gate sits between the depthwise output
 # and the project conv (the kernels of squeeze_excite.hip through ``ops.se_*``, on the padded NHWC
 # layout: a padded channel has y = 0, so its gated value and every gradient there are exact zeros),
-# and the classifier is Linear, Hardswish, Linear. Shapley prefixes are not served: a gate makes the
-# project conv's input non-linear in the channel mask, so the running rank-1 subtraction of
-# ``prefix_logits`` does not hold.
+# and the classifier is Linear, Hardswish, Linear. Shapley prefixes of a gated block go through the
+# channel-scaled project GEMM (``ops.scaled_project``, see "Shapley" below): a gate makes the project
+# conv's input non-linear in the channel mask, so the running rank-1 subtraction does not hold there.
 _ACT_CODES = {nn.ReLU: 1, nn.Hardswish: 3}
-V3_SHAPLEY_REASON = ("mobilenet engine: Shapley on a MobileNetV3 is not served (a squeeze-and-excitation gate makes "
-                     "the project conv's input non-linear in the channel mask, so the prefix scan does not hold)")
+V3_SHAPLEY_REASON = ("mobilenet engine: Shapley on a MobileNetV3 evaluates its prefixes on the scaled project GEMM "
+                     "and needs an eval-mode model on a GPU with the native extension")
 
 
 @dataclass
@@ -652,8 +653,27 @@ def _hs_slope(v: torch.Tensor) -> torch.Tensor:
     return torch.where(v < -3.0, torch.zeros_like(v), torch.where(v <= 3.0, v / 3.0 + 0.5, torch.ones_like(v)))
 
 
+def _gated_operands(rank_t, p0, cnt, pool, fill, q, wt, shift):
+    """(sc (cnt, B, C), bias (cnt, B, Co)) of ``ops.scaled_project`` for the prefixes p0 .. p0+cnt-1 of
+    a gated block: copy j masks the channels of rank < p0 + j. ``pool`` (B, C): the unmasked
+    activation's spatial mean; ``fill`` (C,): the value of a masked channel; ``q``: the gate pack
+    (w1, b1, w2, b2, code); ``wt`` (C, Co), ``shift`` (Co,): the folded project conv. The mask is
+    folded into both: a masked channel has scale 0 and adds fill * gate to the bias product, which
+    runs on the same GEMM (one row per copy and image)."""
+    B, C = pool.shape
+    lim = torch.arange(p0, p0 + cnt, device=pool.device, dtype=rank_t.dtype).view(cnt, 1, 1)
+    masked = (rank_t.view(1, 1, C) < lim).expand(cnt, B, C)
+    zero = torch.zeros((), dtype=pool.dtype, device=pool.device)
+    p = torch.where(masked, fill, pool.unsqueeze(0))
+    _, s = ops.se_gate_fwd(p.reshape(cnt * B, C), q["w1"], q["b1"], q["w2"], q["b2"], q["code"])
+    sc = torch.where(masked, zero, s.view(cnt, B, C))
+    fsc = torch.where(masked, fill, zero).reshape(1, cnt * B, C)
+    bias = ops.scaled_project(s, fsc, wt, shift.expand(1, cnt * B, shift.numel()).contiguous(), None, 1)
+    return sc, bias.view(cnt, B, -1)
+
+
 class MobileNetV3Engine(MobileNetEngine):
-    shapley = False  # attributions/methods/shapley.py: the generic path serves these nets
+    _pooled = None  # (y, se_pool(y)) of the last forward_to on a gated block
 
     def eval_modules(self):
         """The ReLU / Hardswish modules the engine scores: per block the post-expand one (where the
@@ -846,11 +866,128 @@ class MobileNetV3Engine(MobileNetEngine):
             self._arena_sizes[akey] = arena[2]
         return out
 
-    # ------------------------------------------------------------------ Shapley: not served
-    def forward_to(self, *a, **k):
-        raise NotImplementedError(V3_SHAPLEY_REASON)
+    # ------------------------------------------------------------------ partial forward (Shapley)
+    # Copy j of the post-depthwise output y is y with the masked channels at a per-channel constant
+    # ``fill`` (:meth:`prefix_fill`), as on a MobileNetV2. A gate-free block takes the V2 route (linear
+    # project conv, ``ops.prefix_project``). Behind a gate the project input is not linear in the mask,
+    # but all that depends on the copy is small: the pooled mean of copy j is ``fill`` on the masked
+    # channels and y's own mean elsewhere (ONE ``se_pool`` of y), its gate s_j is ``se_gate_fwd`` on
+    # those (cnt * B, C) rows, and
+    #   out_j[n] = (y[n] * sc_j[b]) @ wt + bias_j[b] (+ h[n]),  sc_j = masked ? 0 : s_j,
+    #   bias_j[b] = shift + (masked ? fill * s_j[b] : 0) @ wt
+    # which ``ops.scaled_project`` computes from y alone (``_gated_operands`` builds sc and bias).
+    def forward_to(self, x: torch.Tensor, bi: int):
+        """(block ``bi``'s input h, its post-depthwise activation y, before the gate), in engine
+        layout; a gated block's pooled mean of y is kept for :meth:`prefix_logits`."""
+        T = ops.require()
+        P = self._pack()
+        h, _, in_act = self._stem_out(T, P, x)
+        for b in range(bi):
+            h = self._block(T, self.plan.blocks[b], P["blocks"][b], h, in_act)
+            in_act = 0
+        blk, e = self.plan.blocks[bi], P["blocks"][bi]
+        if blk.expand is not None:
+            z, in_act = self._conv(T, e["expand"], h, False), _act_code(blk.expand.act)
+        else:
+            z = h
+        d = e["dw"]
+        y = T.dwconv_hs_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, _act_code(blk.dw.act),
+                            None, None)
+        self._pooled = (y, ops.se_pool(y)) if blk.gate is not None else None
+        return h, y
 
-    prefix_logits = logits_from = block_logits = prefix_fill = forward_to
+    def _pool_of(self, y):
+        """The spatial mean of ``y``: the one :meth:`forward_to` kept when ``y`` is its result."""
+        kept = self._pooled
+        return kept[1] if kept is not None and kept[0] is y else ops.se_pool(y)
+
+    def prefix_fill(self, bi: int, kind: str) -> torch.Tensor:
+        """(C_padded,) value a masked channel of block ``bi``'s post-depthwise output takes: zeros
+        for ``"dw"``; for ``"expand"`` the depthwise unit's activation (ReLU or Hardswish) of its
+        folded BN shift (a zeroed input channel leaves the depthwise conv 0 at every pixel)."""
+        d = self._pack()["blocks"][bi]["dw"]
+        key = "fill_" + kind
+        if key not in d:
+            if kind == "dw":
+                d[key] = torch.zeros_like(d["shift"])
+            else:
+                act = F.relu if _act_code(self.plan.blocks[bi].dw.act) == 1 else F.hardswish
+                d[key] = act(d["shift"]).contiguous()
+        return d[key]
+
+    def _tail_elems(self, bi: int, H: int, W: int) -> int:
+        # the head is followed by the pooled Linear, Hardswish, Linear: fc1's rows can outgrow a 1x1 head map
+        return max(super()._tail_elems(bi, H, W), cpad(self.plan.fc1.weight.shape[0]))
+
+    def logits_from(self, bi: int, out: torch.Tensor) -> torch.Tensor:
+        T = ops.require()
+        P = self._pack()
+        step = max(1, ((1 << 31) - 1) // (4 * self._tail_elems(bi, out.shape[1], out.shape[2])))
+        logits = []
+        for s in range(0, out.shape[0], step):
+            h = out[s:s + step]
+            for b in range(bi + 1, len(self.plan.blocks)):
+                h = self._block(T, self.plan.blocks[b], P["blocks"][b], h, 0)
+            logits.append(self._head(T, P, h)[0])
+        return logits[0] if len(logits) == 1 else torch.cat(logits, 0)
+
+    def _block_tail(self, T, blk, e, y, res):
+        """Gate, scale and project conv of :meth:`_block` on a (possibly stacked) activation y."""
+        if blk.gate is not None:
+            q = e["gate"]
+            _, sg = ops.se_gate_fwd(self._pool_of(y), q["w1"], q["b1"], q["w2"], q["b2"], q["code"])
+            y = ops.se_scale(y, sg)
+        return self._conv(T, e["project"], y, False, res=res)
+
+    def block_logits(self, bi: int, h: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        blk, e = self.plan.blocks[bi], self._pack()["blocks"][bi]
+        return self.logits_from(bi, self._block_tail(ops.require(), blk, e, y, h if blk.shortcut else None))
+
+    @staticmethod
+    def _use_scaled_project() -> bool:
+        """``TORCHPRUNER_PREFIX_GATED`` (read per call; default 1): 0 takes the composed path (the cnt
+        filled copies, gated, through the project conv) instead of the scaled project GEMM. The GEMM
+        was measured ahead at every gated project shape of MobileNetV3-large
+        (profiles/mobilenet_v3/shapley_engine_vs_hook.txt), so no shape is routed away from it."""
+        return os.environ.get("TORCHPRUNER_PREFIX_GATED", "1") != "0"
+
+    def prefix_project_out(self, bi: int, kind: str, h: torch.Tensor, y: torch.Tensor, rank_t: torch.Tensor, p0: int,
+                           cnt: int) -> torch.Tensor:
+        """The project stage of :meth:`prefix_logits` on a gated block: the (cnt * B, Ho, Wo, Co)
+        stacked block outputs, on the path :meth:`_use_scaled_project` picks."""
+        T = ops.require()
+        blk, e = self.plan.blocks[bi], self._pack()["blocks"][bi]
+        B, Ho, Wo, C = y.shape
+        fill = self.prefix_fill(bi, kind)
+        res = h if blk.shortcut else None
+        co = e["project"]["scale"].numel()
+        if self._use_scaled_project():
+            pe = self._bwd_operands(e["project"])  # wt: (C, Cout) with the BN scale folded in
+            sc, bias = _gated_operands(rank_t, p0, cnt, self._pool_of(y), fill, e["gate"], pe["wt"], pe["shift"])
+            out = ops.scaled_project(y.view(B * Ho * Wo, C), sc, pe["wt"], bias,
+                                     None if res is None else res.view(B * Ho * Wo, co), Ho * Wo)
+            return out.view(cnt * B, Ho, Wo, co)
+        lim = torch.arange(p0, p0 + cnt, device=y.device, dtype=rank_t.dtype).view(cnt, 1, 1, 1, 1)
+        ys = torch.where(rank_t.view(1, 1, 1, 1, C) < lim, fill, y.unsqueeze(0)).view(cnt * B, Ho, Wo, C)
+        if res is not None and cnt > 1:
+            res = res.repeat(cnt, 1, 1, 1)
+        return self._block_tail(T, blk, e, ys, res)
+
+    def prefix_logits(self, bi: int, kind: str, h: torch.Tensor, y: torch.Tensor, perm_t: torch.Tensor,
+                      rank_t: torch.Tensor, p0: int, cnt: int) -> torch.Tensor:
+        """As :meth:`MobileNetEngine.prefix_logits`. A gate-free block takes that route with this
+        engine's ``fill``; a gated one :meth:`prefix_project_out`."""
+        if self.plan.blocks[bi].gate is None:
+            return super().prefix_logits(bi, kind, h, y, perm_t, rank_t, p0, cnt)
+        B, Ho, Wo, C = y.shape
+        co = self._pack()["blocks"][bi]["project"]["scale"].numel()
+        gated = self._use_scaled_project()
+        # copies per piece: the stacked output, sc (and, composed, the stacked input) below 2^31 bytes
+        piece = max(1, ((1 << 31) - 1) // (4 * B * max(Ho * Wo * co, C if gated else Ho * Wo * C)))
+        if cnt > piece:
+            return torch.cat([self.prefix_logits(bi, kind, h, y, perm_t, rank_t, p0 + j, min(piece, cnt - j))
+                              for j in range(0, cnt, piece)], 0)
+        return self.logits_from(bi, self.prefix_project_out(bi, kind, h, y, rank_t, p0, cnt))
 
 
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
@@ -870,15 +1007,15 @@ def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, sh
     """A MobileNetEngine (MobileNetV2 layout) or MobileNetV3Engine when every eval module is a block
     activation the engine serves, else None (``why`` receives the reason). ``grad`` is accepted for
     symmetry with the ResNet engine: the same modules are served forward (APoZ) and backward
-    (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation, which a MobileNetV3 does
-    not get (``V3_SHAPLEY_REASON``)."""
+    (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation; where the engine cannot run,
+    a MobileNetV3 is told what its prefixes need (``V3_SHAPLEY_REASON``)."""
     from .fused_chain import _reject, engines_enabled
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if not engines_enabled():
         return _reject(why, "mobilenet engine: engines disabled (TORCHPRUNER_ENGINES=0)")
-    if shapley and build_mobilenet_plan(model)[0] is None and build_mobilenet_v3_plan(model)[0] is not None:
-        return _reject(why, V3_SHAPLEY_REASON)
     if dev.type != "cuda" or ops.backend() == "torch" or not ops.available() or model.training:
+        if shapley and build_mobilenet_plan(model)[0] is None and build_mobilenet_v3_plan(model)[0] is not None:
+            return _reject(why, V3_SHAPLEY_REASON)
         return _reject(why, "mobilenet engine: needs an eval-mode model on a GPU with the native extension")
     if any(p.dtype != torch.float32 for p in model.parameters()):
         return _reject(why, "mobilenet engine: parameters are not float32")
