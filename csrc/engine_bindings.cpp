@@ -834,6 +834,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_fwd(
 // forward output y when it was ReLU'd (the gradient is masked by y > 0 first); ``want_dres``:
 // also return that masked gradient (the residual branch's gradient). ``act``: the forward's
 // activation code; a ReLU6 forward (2) is masked by its bit mask only ("y > 0" is wrong for it).
+// With neither ``ym`` nor ``mask``, dres is g unchanged, channels c >= cr included (dx is 0 there):
+// callers keep g zero in the padding.
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_train_bwd(
     const at::Tensor& g, const at::Tensor& x, const OptTensor& gamma, const at::Tensor& mean,
     const at::Tensor& invstd, bool want_dx, const OptTensor& ym, bool want_dres, const OptTensor& mask, int64_t cr,

@@ -15,6 +15,21 @@
 //
 // A block owns a 64-wide column quad range (16 threads x float4) x 16 row lanes, and walks
 // rows_per_group rows; the 16 row lanes are folded in LDS in a fixed order.
+//
+// Conditioning of the statistics. A thread adds R = ceil(rows_per_group / 16) values of x and of x^2
+// in fp32 (everything after that is fp64), and the variance is q/P - m^2, so its relative error is
+// bounded by (R + 2) * 2^-24 * mean(x^2) / var: it grows with (mean / std)^2. Measured on an MI355X
+// with x = randn + ratio, C = 8 (tests/test_bn_train_direct_gpu.py::test_conditioning; the last
+// column is F.batch_norm in fp32 on the same device and input, a reference point):
+//   mean/std   P     R   bound     this kernel   F.batch_norm
+//   1/3        200   5   5.1e-07   3.9e-08       9.9e-08
+//   1/3        3136  4   4.0e-07   4.7e-08       1.1e-07
+//   10         200   5   5.0e-05   2.9e-06       3.6e-07
+//   10         3136  4   3.7e-05   5.1e-07       1.8e-07
+//   100        200   5   5.0e-03   1.6e-04       2.9e-06
+//   100        3136  4   3.7e-03   3.3e-05       6.9e-07
+// Inside the bound at every ratio, so the plain sums stay: a shifted or Welford accumulation would
+// change the conv epilogues' tile-statistics contract (``pre``) and every training trajectory.
 #include <type_traits>
 
 #include "tp_common.h"
@@ -230,7 +245,10 @@ __global__ __launch_bounds__(BN_FIN_T) void bn_fwd_finalize(const double* __rest
   fold_groups(part, groups, C, c, cl, gl, lanes, s, q);
   if (gl != 0 || c >= C) return;
   const double m = s / P;
-  const double var = fmax(q / P - m * m, 0.0);
+  // clamped at 0 by a comparison, not fmax(): fmax(NaN, 0) is 0, which gave a channel holding a NaN
+  // or an inf a finite invstd (1/sqrt(eps)) and a finite running_var; a NaN stays a NaN here
+  const double v0 = q / P - m * m;
+  const double var = v0 < 0.0 ? 0.0 : v0;
   const float is = (float)(1.0 / sqrt(var + (double)eps));
   mean[c] = (float)m;
   invstd[c] = is;
@@ -686,6 +704,10 @@ extern "C" hipError_t tp_bn_fwd_train_pre(const float* x, float* y, int P, int C
 // Backward of the fused tail: ym = the block output y (ReLU mask; nullable), dres = gradient of
 // the residual input (nullable). dx nullable (dgamma / dbeta only). Channels c >= Cr: padding
 // (dx = 0 there, no dgamma / dbeta written).
+// dres is the masked g and nothing else: with a mask (mk, whose padding bits are 0, or ym, which is 0
+// there) it is 0 in the padding; with no mask at all (ym and mk null) it is g unchanged, bit for bit,
+// padding included, so callers keep g zero there (the only such caller, the MobileNet project BN of
+// engine/train.py, runs at the module's width, Cr == C).
 // mk (nullable): the forward's ReLU bit mask, used instead of ym
 extern "C" hipError_t tp_bn_bwd_train(const float* g, const float* x, float* dx, int P, int C, int Cr,
                                       const float* gamma, const float* mean, const float* invstd, float* dgamma,
