@@ -969,7 +969,98 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_silu_bwd(const at::Tensor& g, 
   return bn_unit_bwd(&tp_bn_silu_bwd_train, "bn_silu_bwd", g, x, gamma, mean, invstd, ab, want_dx, cr);
 }
 
+// ---- dwconv_silu.hip: the LDS-staged SiLU depthwise kernels of the EfficientNet engine ----
+// shapes shared by the forward and the dgrad: `a` is the conv's (B, H, W, C) input-side operand
+struct DwsShape {
+  int64_t B, H, W, C, k, Ho, Wo;
+};
+DwsShape dws_shape(const at::Tensor& a, const char* name, const at::Tensor& w, const at::Tensor& scale,
+                   const at::Tensor* shift, int64_t s, int64_t pad, int64_t in_act, int64_t out_act) {
+  need(a, name, 4);
+  TORCH_CHECK(a.numel() > 0 && a.numel() < (int64_t(1) << 29), name, " must be non-empty and below 2 GiB");
+  DwsShape d{a.size(0), a.size(1), a.size(2), a.size(3), 0, 0, 0};
+  TORCH_CHECK(d.C % 4 == 0, "dwconv_silu needs a channel count that is a multiple of 4 (pad the channels), got ", d.C);
+  need(w, "w", 4, &a);
+  TORCH_CHECK(w.size(0) == d.C && w.size(1) == 1 && w.size(2) == w.size(3), "w must be a (C, 1, k, k) depthwise weight");
+  need(scale, "scale", 1, &a);
+  TORCH_CHECK(scale.size(0) == d.C, "scale must be a (C,) tensor");
+  if (shift != nullptr) {
+    need(*shift, "shift", 1, &a);
+    TORCH_CHECK(shift->size(0) == d.C, "shift must be a (C,) tensor");
+  }
+  TORCH_CHECK((in_act == 0 || in_act == 4) && out_act == 4,
+              "activation codes are 0 (none) or 4 (SiLU) for in_act and 4 for out_act, got ", in_act, " / ", out_act);
+  d.k = w.size(2);
+  TORCH_CHECK((d.k == 3 || d.k == 5) && (s == 1 || s == 2) && pad >= 0 && pad <= d.k - 1 && d.H + 2 * pad >= d.k &&
+                  d.W + 2 * pad >= d.k,
+              "bad depthwise conv geometry: k ", d.k, " stride ", s, " pad ", pad, " on ", d.H, "x", d.W);
+  d.Ho = (d.H + 2 * pad - d.k) / s + 1, d.Wo = (d.W + 2 * pad - d.k) / s + 1;
+  return d;
+}
+
+// 0 for a shape the kernels reject (the launchers' contract), out of int range included
+int64_t dws_slots(int64_t H, int64_t W, int64_t C) {
+  const int64_t lim = int64_t(1) << 29;
+  if (H < 1 || W < 1 || C < 1 || H >= lim || W >= lim || C >= lim) return 0;
+  return tp_dwconv_silu_tay_slots((int)H, (int)W, (int)C);
+}
+
+// a zeroed (R, B, C) one-writer partial slab (nullable)
+float* dws_slab(const OptTensor& t, const char* name, int64_t R, int64_t B, int64_t C, const at::Tensor& like) {
+  if (!present(t)) return nullptr;
+  need(*t, name, 3, &like);
+  TORCH_CHECK(t->size(0) == R && t->size(1) == B && t->size(2) == C && t->numel() < (int64_t(1) << 29), name,
+              " must be a contiguous (", R, ", ", B, ", ", C, ") slab (slots from dwconv_silu_*_slots)");
+  return t->data_ptr<float>();
+}
+
+// y = silu(v), v = scale * dwconv(in_act(x)) + shift; pre <- v; apoz (B, C) += count(y > 0); pool: zeroed
+// (dwconv_silu_pool_slots(Ho, Wo, C), B, C) slab of partial sums of y over the map
+at::Tensor dwconv_silu_fwd(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
+                           int64_t s, int64_t pad, int64_t in_act, int64_t out_act, const OptTensor& apoz,
+                           const OptTensor& pre, const OptTensor& pool) {
+  const DwsShape d = dws_shape(x, "x", w, scale, &shift, s, pad, in_act, out_act);
+  float* ap = count_ptr(apoz, d.B, d.C, x);
+  const float* pp = nhwc_ptr(pre, "pre", d.B, d.Ho, d.Wo, d.C, x);
+  const int64_t Rp = present(pool) ? dws_slots(d.Ho, d.Wo, d.C) : 0;
+  float* pl = dws_slab(pool, "pool", Rp, d.B, d.C, x);
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty({d.B, d.Ho, d.Wo, d.C}, x.options());
+  TP_CHECK_HIP(tp_dwconv_silu_fwd(x.data_ptr<float>(), w.data_ptr<float>(), scale.data_ptr<float>(),
+                                  shift.data_ptr<float>(), y.data_ptr<float>(), const_cast<float*>(pp), ap, pl, (int)Rp,
+                                  (int)d.B, (int)d.H, (int)d.W, (int)d.C, (int)d.k, (int)s, (int)pad, (int)in_act,
+                                  (int)out_act, cur_stream()));
+  return y;
+}
+
+// dz = dA * in_act'(z), dA = dwconv^T(g * scale * silu'(v)), v the forward's `pre`; tay: zeroed
+// (dwconv_silu_tay_slots(H, W, C), B, C) slab of partial sums of -(dA * in_act(z)) (tay_mode 0) or |dA| (1)
+at::Tensor dwconv_silu_dgrad(const at::Tensor& g, const at::Tensor& v, const at::Tensor& w, const at::Tensor& scale,
+                             const at::Tensor& z, int64_t H, int64_t W, int64_t s, int64_t pad, int64_t in_act,
+                             int64_t out_act, const OptTensor& tay, int64_t tay_mode) {
+  const DwsShape d = dws_shape(z, "z", w, scale, nullptr, s, pad, in_act, out_act);
+  TORCH_CHECK(d.H == H && d.W == W, "z must be a contiguous (B, H, W, C) tensor");
+  TORCH_CHECK(nhwc_ptr(g, "g", d.B, d.Ho, d.Wo, d.C, z) != nullptr, "g is required");
+  TORCH_CHECK(nhwc_ptr(v, "v", d.B, d.Ho, d.Wo, d.C, z) != nullptr, "v (the forward's pre) is required");
+  const int mode = present(tay) ? tay_mode_arg(tay_mode, 1) : 0;
+  const int64_t R = present(tay) ? dws_slots(H, W, d.C) : 0;
+  float* tp = dws_slab(tay, "tay", R, d.B, d.C, z);
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto dz = at::empty_like(z);
+  TP_CHECK_HIP(tp_dwconv_silu_dgrad(g.data_ptr<float>(), v.data_ptr<float>(), w.data_ptr<float>(),
+                                    scale.data_ptr<float>(), z.data_ptr<float>(), dz.data_ptr<float>(), tp, (int)R, mode,
+                                    (int)d.B, (int)d.H, (int)d.W, (int)d.C, (int)d.k, (int)s, (int)pad, (int)in_act,
+                                    (int)out_act, cur_stream()));
+  return dz;
+}
+
 void register_engine_ops_def(torch::Library& m) {
+  m.def("dwconv_silu_fwd(Tensor x, Tensor w, Tensor scale, Tensor shift, int stride, int pad, int in_act, "
+        "int out_act, Tensor(a!)? apoz=None, Tensor(b!)? pre=None, Tensor(c!)? pool=None) -> Tensor");
+  m.def("dwconv_silu_dgrad(Tensor g, Tensor v, Tensor w, Tensor scale, Tensor z, int H, int W, int stride, int pad, "
+        "int in_act, int out_act, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
+  m.def("dwconv_silu_tay_slots(int H, int W, int C) -> int", &dws_slots);
+  m.def("dwconv_silu_pool_slots(int Ho, int Wo, int C) -> int", &dws_slots);
   m.def("wino_taylor_slots(int H, int W) -> int", &wino_taylor_slots);
   m.def("wino_lds_bytes() -> int", []() -> int64_t { return tp_wino_lds_bytes(); });
   m.def("wino_staged_ok(int H, int W, bool unpool) -> bool",
@@ -1039,6 +1130,8 @@ void register_engine_ops_def(torch::Library& m) {
 }
 
 void register_engine_ops_impl(torch::Library& m) {
+  m.impl("dwconv_silu_fwd", &dwconv_silu_fwd);
+  m.impl("dwconv_silu_dgrad", &dwconv_silu_dgrad);
   m.impl("conv_fwd", &conv_fwd);
   m.impl("conv_dgrad", &conv_dgrad);
   m.impl("conv2x2_fast_fwd", &conv2x2_fast_fwd);

@@ -126,6 +126,17 @@ int tp_dwconv_hs_tay_slots(int H, int W, int C);
 hipError_t tp_dwconv_hs_dgrad(const float* g, const float* y, const float* w, const float* scale, const float* z,
                               float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
                               int pad, int in_act, int out_act, hipStream_t st);
+// dwconv_silu.hip (C % 4 == 0; activation codes 0 none, 4 SiLU; out_act is 4): LDS-staged kernels. pre
+// (optional): the output's pre-activation, the v operand of the dgrad; pool (optional): a zeroed
+// (Rp, B, C) slab of per-block sums of y, Rp = tp_dwconv_silu_pool_slots(Ho, Wo, C)
+int tp_dwconv_silu_pool_slots(int Ho, int Wo, int C);
+int tp_dwconv_silu_tay_slots(int H, int W, int C);
+hipError_t tp_dwconv_silu_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
+                              float* pre, float* apoz, float* pool, int Rp, int B, int H, int W, int C, int k, int s,
+                              int pad, int in_act, int out_act, hipStream_t st);
+hipError_t tp_dwconv_silu_dgrad(const float* g, const float* v, const float* w, const float* scale, const float* z,
+                                float* dz, float* tay, int R, int tay_mode, int B, int H, int W, int C, int k, int s,
+                                int pad, int in_act, int out_act, hipStream_t st);
 // prefix_project.hip: out[0] = base, out[j] = out[j-1] - (a[:, c] - fill[c]) (x) wt[c, :], c = perm[p0+j-1]
 // (base (N, Co), a (N, C), fill (C), wt (C, Co), perm (n <= C), out (cnt, N, Co); Co % 4 == 0)
 hipError_t tp_prefix_project(const float* base, const float* a, const float* fill, const float* wt, const int* perm,

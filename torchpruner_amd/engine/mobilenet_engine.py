@@ -35,6 +35,11 @@ the same way with ReLU / Hardswish units (``tpamd.dwconv_hs_*``), the squeeze-an
 between the depthwise output and the project conv, and a two-layer classifier; the Shapley prefixes
 of a gated block are per-(copy, image, channel) scales and biases of ONE hidden activation
 (``ops.scaled_project``, csrc/kernels/scaled_project.hip).
+
+EfficientNets (``build_efficientnet_plan`` / ``EfficientNetEngine``, last part of this file) run the
+same way with SiLU units on the LDS-staged depthwise kernels (``tpamd.dwconv_silu_*``,
+csrc/kernels/dwconv_silu.hip), whose forward also leaves the gate's pool partials; APoZ, Taylor and
+Sensitivity only (Shapley stays on the generic path).
 """
 from __future__ import annotations
 
@@ -990,6 +995,261 @@ class MobileNetV3Engine(MobileNetEngine):
         return self.logits_from(bi, self.prefix_project_out(bi, kind, h, y, rank_t, p0, cnt))
 
 
+# ====================================================================== EfficientNet
+# The same engine for the torchvision / models.efficientnet layout: every unit is (conv, BN, SiLU),
+# stages are plain Sequentials of MBConv blocks, every block has a gate with a SiLU inside
+# (``ops.se_gate_act_*``, inner code 1) and the classifier is one Linear. The depthwise unit runs the
+# LDS-staged kernels of dwconv_silu.hip (``tpamd.dwconv_silu_*``): the forward stores the
+# pre-activation for the backward and the per-block sums of its output, which are the gate's pooled
+# mean (no ``se_pool`` pass over the activation it just wrote). Taylor, Sensitivity and APoZ only.
+_SILU = 4
+EFFNET_SHAPLEY_REASON = ("mobilenet engine: Shapley on an EfficientNet is not lowered (the engine serves APoZ, Taylor "
+                         "and Sensitivity there); the generic path evaluates its prefixes")
+
+
+@dataclass
+class EfficientNetPlan:
+    stem: _Unit
+    head: _Unit
+    fc: nn.Linear
+    blocks: list = field(default_factory=list)
+
+
+def _unit_silu(seq, what):
+    """(_Unit, "") of a conv-BN-SiLU Sequential, else (None, reason)."""
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        return None, f"{what}: expected a (conv, BN, SiLU) Sequential"
+    conv, bn, act = seq
+    kind = _conv_kind(conv)
+    if kind not in ("dense", "depthwise"):
+        return None, f"{what}: {kind}"
+    if not isinstance(bn, nn.BatchNorm2d) or bn.running_mean is None:
+        return None, f"{what}: expected a BatchNorm2d with running statistics after the conv"
+    if type(act) is not nn.SiLU:
+        return None, f"{what}: activation {type(act).__name__} is not supported (only SiLU)"
+    return _Unit(conv, bn, act), ""
+
+
+def build_efficientnet_plan(model: nn.Module):
+    """Lower a torchvision-layout EfficientNet (``models.efficientnet``), or return (None, reason).
+    Structural: widths are read from the tensors; ``stochastic_depth`` is the identity in eval mode."""
+    from ..utils.graph import is_channel_gate
+    from .train import _se_codes
+    feats, cls = getattr(model, "features", None), getattr(model, "classifier", None)
+    stages = list(feats[1:-1]) if isinstance(feats, nn.Sequential) and len(feats) >= 3 else []
+    if not stages or cls is None or not all(isinstance(st, nn.Sequential) and len(st) > 0 and all(
+            isinstance(getattr(b, "block", None), nn.Sequential) for b in st) for st in stages):
+        return None, "not a torchvision-layout EfficientNet (features / stages of MBConv `.block`s / classifier)"
+    pool = getattr(model, "avgpool", None)
+    if pool is not None and not (isinstance(pool, nn.AdaptiveAvgPool2d) and pool.output_size in (1, (1, 1))):
+        return None, "avgpool: unsupported pool before the classifier (needs a global AdaptiveAvgPool2d)"
+    layers = list(cls.children()) if isinstance(cls, nn.Sequential) else [cls]
+    if not layers or not isinstance(layers[-1], nn.Linear) or not all(isinstance(m, nn.Dropout) for m in layers[:-1]):
+        return None, "classifier: unsupported shape (needs Dropout layers and a final Linear)"
+    stem, why = _unit_silu(feats[0], "features.0 (stem)")
+    if stem is None:
+        return None, why
+    if _conv_kind(stem.conv) != "dense" or stem.conv.weight.shape[2] != 3 or stem.conv.weight.shape[1] > 4 or \
+            stem.conv.padding[0] != 1:
+        return None, "features.0 (stem): needs a 3x3 conv, padding 1, of at most 4 input channels"
+    last = len(feats) - 1
+    head, why = _unit_silu(feats[-1], f"features.{last} (head)")
+    if head is None:
+        return None, why
+    if _conv_kind(head.conv) != "dense" or not _is_1x1(head.conv):
+        return None, f"features.{last} (head): needs a 1x1 conv"
+    plan = EfficientNetPlan(stem, head, layers[-1])
+    width = stem.conv.weight.shape[0]
+    shape = "([1x1-BN-SiLU,] depthwise-BN-SiLU, gate, (1x1, BN))"
+    for si, stage in enumerate(stages, 1):
+        for bi, blk in enumerate(stage):
+            what = f"features.{si}.{bi}"
+            items = list(blk.block)
+            if len(items) not in (3, 4) or not is_channel_gate(items[-2]) or \
+                    not isinstance(items[-1], nn.Sequential) or len(items[-1]) != 2:
+                return None, f"{what}: expected an MBConv `.block` {shape}"
+            expand = None
+            if len(items) == 4:
+                expand, why = _unit_silu(items[0], f"{what}.block.0 (expand)")
+                if expand is None:
+                    return None, why
+                if _conv_kind(expand.conv) != "dense" or not _is_1x1(expand.conv):
+                    return None, f"{what}.block.0: the expand conv must be a dense 1x1 conv"
+            di = len(items) - 3
+            dw, why = _unit_silu(items[di], f"{what}.block.{di} (depthwise)")
+            if dw is None:
+                return None, why
+            k, s, pd = dw.conv.weight.shape[2], dw.conv.stride[0], dw.conv.padding[0]
+            if _conv_kind(dw.conv) != "depthwise" or k not in (3, 5) or s not in (1, 2) or pd > k - 1:
+                return None, (f"{what}.block.{di}: the depthwise conv must be 3x3 / 5x5, stride 1 / 2, padding < k, "
+                              "depth multiplier 1")
+            hidden = dw.conv.weight.shape[0]
+            gate = items[-2]
+            codes = _se_codes(gate)
+            if codes is None or codes[1] != 1:
+                inner = ", ".join(f"{n} {type(getattr(gate, n, None)).__name__}"
+                                  for n in ("avgpool", "activation", "scale_activation"))
+                return None, (f"{what}.block.{di + 1}: unsupported gate ({inner}; needs a global average pool, a SiLU "
+                              "and a Sigmoid or Hardsigmoid)")
+            if gate.fc1.weight.shape[1] != hidden or gate.fc2.weight.shape[1] != gate.fc1.weight.shape[0] or \
+                    gate.fc2.weight.shape[0] != hidden:
+                return None, f"{what}.block.{di + 1}: the gate's fc widths do not chain with the block's hidden width"
+            if cpad(hidden) + gate.fc1.weight.shape[0] > ops.se.SE_MAX_FC:
+                return None, f"{what}.block.{di + 1}: the gate's widths exceed {ops.se.SE_MAX_FC}"
+            pconv, pbn = items[-1]
+            kind = _conv_kind(pconv)
+            if kind != "dense" or not _is_1x1(pconv):
+                return None, f"{what}: the project conv must be a dense 1x1 conv" + \
+                    ("" if kind == "dense" else f" ({kind})")
+            if not isinstance(pbn, nn.BatchNorm2d) or pbn.running_mean is None:
+                return None, f"{what}: expected a BatchNorm2d with running statistics after the project conv"
+            if (expand.conv.weight.shape[:2] if expand else (hidden, width)) != (hidden, width) or \
+                    pconv.weight.shape[1] != hidden:
+                return None, f"{what}: channel counts of the block's convs do not chain"
+            cout = pconv.weight.shape[0]
+            shortcut = getattr(blk, "use_res_connect", None)
+            if shortcut is None:
+                shortcut = s == 1 and cout == width
+            if shortcut and (s != 1 or cout != width):
+                return None, f"{what}: a shortcut needs stride 1 and equal widths"
+            plan.blocks.append(_V3Block(expand, dw, gate, _Conv(pconv, pbn), bool(shortcut)))
+            width = cout
+    if head.conv.weight.shape[1] != width or plan.fc.weight.shape[1] != head.conv.weight.shape[0]:
+        return None, "channel counts of the head / classifier do not chain"
+    return plan, ""
+
+
+def _silu_slope(v: torch.Tensor) -> torch.Tensor:
+    s = torch.sigmoid(v)
+    return s * (1.0 + v * (1.0 - s))
+
+
+class EfficientNetEngine(MobileNetV3Engine):
+    # eval_modules (inherited): the SiLU modules after a block's expand conv (where it expands) and
+    # after its depthwise conv (before the gate)
+    def _params_key(self):
+        key = list(ResNetEngine._params_key(self))
+        for b in self.plan.blocks:
+            for t in (b.gate.fc1.weight, b.gate.fc1.bias, b.gate.fc2.weight, b.gate.fc2.bias):
+                if t is not None:
+                    key.append((t.data_ptr(), t._version, tuple(t.shape)))
+        return tuple(key)
+
+    def _pack_gate(self, gate):
+        from .train import _se_codes
+        q = super()._pack_gate(gate)
+        q["code"] = _se_codes(gate)[0]
+        return q
+
+    def _pack(self):
+        key = self._params_key()
+        if key == self._key:
+            return self._packed
+        gates = [self._pack_gate(b.gate) for b in self.plan.blocks]
+        P = MobileNetEngine._pack(self)  # convs, depthwise units and the single classifier Linear
+        for e, q in zip(P["blocks"], gates):
+            e["gate"] = q
+        return P
+
+    # ------------------------------------------------------------------ forward
+    def _block(self, T, blk, e, h, in_act, apoz=None, saved=None):
+        """One MBConv block from its (linear, or for a fused stem pre-activation) input ``h``; appends
+        (input, z, y, input activation code, pre-activation of y, gate state) to ``saved``."""
+        apoz = apoz or {}
+        if blk.expand is not None:
+            z = self._conv(T, e["expand"], h, False, apoz=apoz.get(blk.expand.act))
+            in_act = _SILU
+        else:
+            z = h
+        d = e["dw"]
+        B, H, W, C = z.shape
+        Ho, Wo = _out_hw(blk.dw.conv, H, W)
+        pre = z.new_empty(B, Ho, Wo, C) if saved is not None else None
+        pool = z.new_zeros(T.dwconv_silu_pool_slots(Ho, Wo, C), B, C)
+        y = T.dwconv_silu_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, _SILU,
+                              apoz.get(blk.dw.act), pre, pool)
+        q = e["gate"]
+        pooled = pool[0] if pool.shape[0] == 1 else pool.sum(0)
+        hh, z1, sg = ops.se_gate_act_fwd(pooled.div_(Ho * Wo), q["w1"], q["b1"], q["w2"], q["b2"], q["code"], 1)
+        out = self._conv(T, e["project"], ops.se_scale(y, sg), False, res=h if blk.shortcut else None)
+        if saved is not None:
+            saved.append((h, z, y, in_act, pre, (hh, z1, sg)))
+        return out
+
+    def _stem_out(self, T, P, x):
+        h = T.nchw_to_nhwc_pad(x.float().contiguous(), 4)
+        h = self._conv(T, P["stem"], h, False)
+        if self._stem_fused():
+            return h, None, _SILU
+        return F.silu(h), h, 0
+
+    def _head(self, T, P, h):
+        zh = self._conv(T, P["head"], h, False)
+        return self._fc(T, P, T.avgpool_nhwc(F.silu(zh))), zh, None
+
+    # ------------------------------------------------------------------ backward (Taylor, Sensitivity)
+    def grad_scores(self, x: torch.Tensor, y: torch.Tensor, want, mode: str, criterion=None,
+                    loss_batch: Optional[int] = None, raw_slabs: bool = False):
+        """As :meth:`MobileNetV3Engine.grad_scores`, with SiLU's derivative at the head and the
+        SiLU-inside gate's backward."""
+        T = ops.require()
+        P = self._pack()
+        logits, saved = self.forward(x, save=True)
+        zh, _, _ = saved.pop()
+        B = logits.shape[0]
+        blocks = self.plan.blocks
+        first = min((bi for bi, b in enumerate(blocks)
+                     if b.dw.act in want or (b.expand is not None and b.expand.act in want)), default=None)
+        out = {}
+        if first is None:
+            return out
+        g_log = logits_grad(logits, y, criterion, loss_batch)
+        # the GEMM kernel's mask operand is all ones: the pooled SiLU outputs carry no ReLU mask
+        g_feat = self._fc_bwd(T, P, g_log, zh.new_ones(B, zh.shape[3]))
+        HW = zh.shape[1] * zh.shape[2]
+        g = (g_feat / HW)[:, None, None, :] * _silu_slope(zh)  # avg-pool backward + the head's SiLU
+        g, _ = self._dgrad(T, P["head"], g.contiguous(), None)
+        akey = (tuple(x.shape), mode, tuple(sorted(i for i, m in enumerate(self.eval_modules()) if m in want)))
+        size = self._arena_sizes.get(akey)
+        arena = [torch.zeros(size, device=x.device) if size else None, 0, 0]
+        for bi in range(len(blocks) - 1, first - 1, -1):
+            blk, e = blocks[bi], P["blocks"][bi]
+            h, z, yd, in_act, pre, (hh, z1, sg) = saved[bi]
+            q = e["gate"]
+            gy, _ = self._dgrad(T, e["project"], g, None)  # dL/d(project input), unfactored
+            _, _, dp = ops.se_gate_act_bwd(ops.se_bwd_reduce(gy, yd), sg, hh, z1, q["w1"], q["w2"], q["code"], 1)
+            gy = ops.se_bwd_dx(gy, sg, dp)  # dL/d(depthwise SiLU output)
+            if blk.dw.act in want:
+                out[blk.dw.act] = ops.channel_reduce(yd.permute(0, 3, 1, 2), gy.permute(0, 3, 1, 2), mode)
+            ex_wanted = blk.expand is not None and blk.expand.act in want
+            if bi == first and not ex_wanted:
+                break
+            d = e["dw"]
+            _, H, W, C = z.shape
+            tay = self._slab(arena, T.dwconv_silu_tay_slots(H, W, C), B, C, x.device) if ex_wanted else None
+            dz = T.dwconv_silu_dgrad(gy, pre, d["w"], d["scale"], z, H, W, d["stride"], d["pad"], in_act, _SILU, tay,
+                                     _TAY_MODES[mode])
+            if ex_wanted:
+                if raw_slabs:
+                    out[blk.expand.act] = tay
+                else:
+                    sums = tay.sum(0)
+                    out[blk.expand.act] = sums.abs_() if mode == "taylor" else sums
+            if bi == first:
+                break
+            if blk.expand is not None:  # the block input is linear: no factor
+                g, _ = self._dgrad(T, e["expand"], dz, None, res=g if blk.shortcut else None)
+            else:
+                g = dz + g if blk.shortcut else dz
+        if arena[2] > (size or 0):
+            self._arena_sizes[akey] = arena[2]
+        return out
+
+    # ------------------------------------------------------------------ Shapley: not lowered
+    def forward_to(self, x: torch.Tensor, bi: int):
+        raise NotImplementedError(EFFNET_SHAPLEY_REASON)
+
+
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
 
 
@@ -1004,8 +1264,9 @@ def _engine_sig(eng):
 
 
 def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, shapley=False):
-    """A MobileNetEngine (MobileNetV2 layout) or MobileNetV3Engine when every eval module is a block
-    activation the engine serves, else None (``why`` receives the reason). ``grad`` is accepted for
+    """A MobileNetEngine (MobileNetV2 layout), MobileNetV3Engine or EfficientNetEngine (tried in this
+    order) when every eval module is a block activation the engine serves, else None (``why`` receives
+    the reason; an EfficientNet with ``shapley`` is rejected: ``EFFNET_SHAPLEY_REASON``). ``grad`` is accepted for
     symmetry with the ResNet engine: the same modules are served forward (APoZ) and backward
     (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation; where the engine cannot run,
     a MobileNetV3 is told what its prefixes need (``V3_SHAPLEY_REASON``)."""
@@ -1024,9 +1285,17 @@ def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, sh
     if plan is None:
         plan, reason3 = build_mobilenet_v3_plan(model)
         cls = MobileNetV3Engine
+    if plan is None:
+        plan, reason_e = build_efficientnet_plan(model)
+        cls = EfficientNetEngine
         if plan is None:  # the reason of the layout the model looks like
-            v3 = any(isinstance(getattr(m, "block", None), nn.Sequential) for m in getattr(model, "features", []))
+            feats = list(getattr(model, "features", []))
+            if any(isinstance(m, nn.Sequential) and any(hasattr(b, "block") for b in m) for m in feats[1:-1]):
+                return _reject(why, f"mobilenet engine: {reason_e}")
+            v3 = any(isinstance(getattr(m, "block", None), nn.Sequential) for m in feats)
             return _reject(why, f"mobilenet engine: {reason3 if v3 else reason}")
+        if shapley:
+            return _reject(why, EFFNET_SHAPLEY_REASON)
     new = cls(model, plan)
     eng = _ENGINES.get(model)
     if eng is None or _engine_sig(eng) != _engine_sig(new):
@@ -1035,6 +1304,6 @@ def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, sh
     ok = set(map(id, eng.eval_modules()))
     if not all(id(m) in ok for m in eval_modules):
         return _reject(why, "mobilenet engine: evaluation modules must be the activation (ReLU6; ReLU / Hardswish "
-                            "of a MobileNetV3) after a block's expand or depthwise conv (use "
+                            "of a MobileNetV3; SiLU of an EfficientNet) after a block's expand or depthwise conv (use "
                             "find_best_evaluation_module=True)")
     return eng

@@ -15,6 +15,7 @@ from .bn_hswish import bn_hswish_bwd, bn_hswish_fwd
 from .bn_silu import bn_silu_bwd, bn_silu_fwd
 from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 from .dwconv_hs import dwconv_hs_dgrad, dwconv_hs_fwd, dwconv_hs_tay_slots
+from .dwconv_silu import dwconv_silu_dgrad, dwconv_silu_fwd, dwconv_silu_pool_slots, dwconv_silu_tay_slots
 from .scaled_project import scaled_project
 from .se import (SE_ACTS, SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_act_bwd, se_gate_act_fwd, se_gate_bwd,
                  se_gate_fwd, se_pool, se_scale, se_wgrad)
@@ -25,6 +26,7 @@ __all__ = [
     "gather_multi", "prefix_mask", "prefix_project", "scaled_project", "shapley_scatter", "shapley_column", "cross_entropy",
     "dwconv_act_fwd", "dwconv_act_dgrad", "dwconv_act_tay_slots",
     "dwconv_hs_fwd", "dwconv_hs_dgrad", "dwconv_hs_tay_slots",
+    "dwconv_silu_fwd", "dwconv_silu_dgrad", "dwconv_silu_tay_slots", "dwconv_silu_pool_slots",
     "SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad",
     "SE_ACTS", "se_gate_act_fwd", "se_gate_act_bwd",
     "bn_hswish_fwd", "bn_hswish_bwd", "bn_silu_fwd", "bn_silu_bwd",
