@@ -1005,6 +1005,17 @@ int64_t dws_slots(int64_t H, int64_t W, int64_t C) {
   return tp_dwconv_silu_tay_slots((int)H, (int)W, (int)C);
 }
 
+// {tw, lq, ncb, bw, nsl, nrb, rbh, slots}: how the launchers cut B (rows x cols x C) maps into blocks; empty
+// for a shape the kernels reject
+std::vector<int64_t> dws_tile_list(int64_t B, int64_t rows, int64_t cols, int64_t C) {
+  const int64_t lim = int64_t(1) << 29;
+  int t[8];
+  if (B < 1 || rows < 1 || cols < 1 || C < 1 || B >= lim || rows >= lim || cols >= lim || C >= lim ||
+      !tp_dwconv_silu_tile((int)B, (int)rows, (int)cols, (int)C, t))
+    return {};
+  return std::vector<int64_t>(t, t + 8);
+}
+
 // a zeroed (R, B, C) one-writer partial slab (nullable)
 float* dws_slab(const OptTensor& t, const char* name, int64_t R, int64_t B, int64_t C, const at::Tensor& like) {
   if (!present(t)) return nullptr;
@@ -1061,6 +1072,7 @@ void register_engine_ops_def(torch::Library& m) {
         "int in_act, int out_act, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
   m.def("dwconv_silu_tay_slots(int H, int W, int C) -> int", &dws_slots);
   m.def("dwconv_silu_pool_slots(int Ho, int Wo, int C) -> int", &dws_slots);
+  m.def("dwconv_silu_tile(int B, int rows, int cols, int C) -> int[]", &dws_tile_list);
   m.def("wino_taylor_slots(int H, int W) -> int", &wino_taylor_slots);
   m.def("wino_lds_bytes() -> int", []() -> int64_t { return tp_wino_lds_bytes(); });
   m.def("wino_staged_ok(int H, int W, bool unpool) -> bool",

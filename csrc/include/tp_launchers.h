@@ -131,6 +131,9 @@ hipError_t tp_dwconv_hs_dgrad(const float* g, const float* y, const float* w, co
 // (Rp, B, C) slab of per-block sums of y, Rp = tp_dwconv_silu_pool_slots(Ho, Wo, C)
 int tp_dwconv_silu_pool_slots(int Ho, int Wo, int C);
 int tp_dwconv_silu_tay_slots(int H, int W, int C);
+// the launchers' split of B (rows x cols x C) maps (forward: the output map, dgrad: the input map):
+// out8 = {tw, lq, ncb, bw, nsl, nrb, rbh, slots}; returns 0 for a rejected shape
+int tp_dwconv_silu_tile(int B, int rows, int cols, int C, int* out8);
 hipError_t tp_dwconv_silu_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y,
                               float* pre, float* apoz, float* pool, int Rp, int B, int H, int W, int C, int k, int s,
                               int pad, int in_act, int out_act, hipStream_t st);

@@ -102,7 +102,7 @@ static bool dws_tile(int B, int rows, int cols, int C, DwsTile* t) {
   t->tw = t->bw <= 8 ? 8 : t->bw <= 16 ? 16 : 32;
   t->lq = t->tw == 8 ? 5 : t->tw == 16 ? 4 : 3;
   t->nsl = (int)ceil_div(C / 4, DWS_T / t->tw);
-  const long long finest = std::max(1, (rows + DWS_MIN_ROWS / 2) / DWS_MIN_ROWS);
+  const long long finest = std::max(1ll, ((long long)rows + DWS_MIN_ROWS / 2) / DWS_MIN_ROWS);  // rows up to INT_MAX
   const long long slots = finest * t->ncb;
   if (slots >= (1ll << 24)) return false;
   t->slots = (int)slots;
@@ -399,6 +399,17 @@ extern "C" int tp_dwconv_silu_pool_slots(int Ho, int Wo, int C) {
 }
 
 extern "C" int tp_dwconv_silu_tay_slots(int H, int W, int C) { return tp_dwconv_silu_pool_slots(H, W, C); }
+
+// How the launchers cut a batch of B (rows x cols x C) maps (the forward's OUTPUT map, the dgrad's INPUT
+// map): out8 = {tw, lq, ncb, bw, nsl, nrb, rbh, slots} of DwsTile. Host only, for the tests, which must
+// know which band a block owns; returns 1, or 0 (out8 untouched) for a shape the kernels reject.
+extern "C" int tp_dwconv_silu_tile(int B, int rows, int cols, int C, int* out8) {
+  tp::DwsTile t;
+  if (out8 == nullptr || !tp::dws_tile(B, rows, cols, C, &t)) return 0;
+  const int v[8] = {t.tw, t.lq, t.ncb, t.bw, t.nsl, t.nrb, t.rbh, t.slots};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  return 1;
+}
 
 // y = silu(v), v = scale * dwconv(in_act(x)) + shift: x (B, H, W, C), w (C, 1, k, k), scale / shift (C),
 // y (B, Ho, Wo, C). Optional: pre (the shape of y) <- v; apoz (B, C) += count(y > 0); pool: a zeroed

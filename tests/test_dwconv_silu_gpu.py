@@ -5,7 +5,9 @@ branch can flip between the two, so the bounds are arithmetic only (those of tes
 Shapes: C no multiple of the 32-channel slice, W wider than one column band, odd H; a stride-2 map with
 pad 2; a map smaller than the kernel; (1, 19, 8, 32): five row bands of the finest split; and the
 tile's remaining boundary, (32, 19, 2, 2048): 512 blocks before the row split, so the rows are cut into
-two bands of 10 and 9 only and the LDS ring (6 rows for 5x5 stride 1) wraps inside a band."""
+two bands of 10 and 9 only and the LDS ring (6 rows for 5x5 stride 1) wraps inside a band. EDGE_SHAPES:
+the band-arithmetic edges of test_dwconv_silu_edges_gpu.py (which asserts their splits and checks them
+bit for bit on integer inputs), here under the real SiLU arithmetic."""
 import pytest
 import torch
 
@@ -15,7 +17,12 @@ KS4 = [(3, 1, 1), (3, 2, 1), (5, 1, 2), (5, 2, 2)]
 SHAPES = [((3, 7, 9, 40), KS4), ((2, 5, 36, 72), KS4), ((2, 5, 5, 32), [(3, 2, 2), (5, 2, 2)]),
           ((2, 1, 1, 36), [(3, 1, 1), (5, 1, 2)]), ((1, 19, 8, 32), [(5, 1, 2), (3, 2, 1)]),
           ((32, 19, 2, 2048), [(5, 1, 2), (3, 2, 1)])]
-CASES = [(shape, ksp) for shape, lst in SHAPES for ksp in lst]
+EDGE_SHAPES = [((1, 8, 33, 8), KS4), ((1, 6, 66, 8), [(3, 2, 1), (5, 2, 2), (3, 1, 1)]),
+               ((1, 4, 65, 8), [(5, 1, 2), (3, 1, 1)]), ((1, 21, 3, 8), KS4),
+               ((2, 12, 12, 8), [(3, 2, 1), (5, 2, 2), (3, 2, 0), (5, 1, 4), (3, 1, 0)]),
+               ((1, 9, 14, 8), [(3, 2, 1), (5, 2, 2), (5, 1, 2)]), ((300, 19, 4, 8), [(5, 1, 2), (3, 2, 1)]),
+               ((2, 10, 16, 136), [(3, 1, 1), (5, 2, 2)])]
+CASES = [(shape, ksp) for shape, lst in SHAPES + EDGE_SHAPES for ksp in lst]
 
 
 def _inputs(shape, k, s, pad, in_act, seed):

@@ -216,6 +216,7 @@ HOST_PROGRAMS = {
     "dwconv_validation": ("dwconv",),
     "dwconv_act_validation": ("dwconv_act",),
     "dwconv_hs_validation": ("dwconv_act",),
+    "dwconv_silu_validation": ("dwconv_silu",),
     "dwconv_carried_validation": ("dwconv", "batchnorm"),
     "se_validation": ("squeeze_excite",),
     "bn_hswish_validation": ("batchnorm",),
