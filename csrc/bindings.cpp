@@ -287,6 +287,93 @@ at::Tensor scaled_project(const at::Tensor& a, const at::Tensor& sc, const at::T
   return out;
 }
 
+// ---- silu_project.hip: the SiLU-on-load project GEMM of a Fused-MBConv block and its data gradient ----
+constexpr int64_t kSiluProjectMaxCo = 128;  // the forward's accumulators: 4 column tiles of 32 per wave
+
+// rows x cols operand of the device of ``like``, read as float4
+void sj_matrix(const at::Tensor& t, const char* name, int64_t rows, int64_t cols, const at::Tensor* like) {
+  need(t, name, 2, like);
+  TORCH_CHECK(t.size(0) == rows && t.size(1) == cols, name, " must be (", rows, ", ", cols, "), got ", t.sizes());
+  need_aligned16(t, name);
+}
+
+// (N, C, Co) of z (N, C) against a (Co-side) operand; every operand below 2^31 bytes
+void sj_sizes(int64_t N, int64_t C, int64_t Co) {
+  TORCH_CHECK(N > 0 && C > 0 && Co > 0, "silu_project: empty operand");
+  TORCH_CHECK(C % 4 == 0 && Co % 4 == 0, "silu_project needs C % 4 == 0 and Co % 4 == 0, got C ", C, " Co ", Co);
+  const int64_t lim = int64_t(1) << 29;  // floats of 2^31 bytes
+  TORCH_CHECK(N < lim && C < lim && Co < lim && N * C < lim && N * Co < lim && C * Co < lim,
+              "silu_project operands must stay below 2^31 bytes");
+}
+
+// out (N, Co) = (silu(z) @ wt) * scale + shift (+ res); apoz (B, C) += counts of silu(z) > 0 per image of N / B rows
+at::Tensor silu_project_fwd(const at::Tensor& z, const at::Tensor& wt, const at::Tensor& scale,
+                            const at::Tensor& shift, const OptTensor& res, const OptTensor& apoz) {
+  need(z, "z", 2);
+  need(wt, "wt", 2, &z);
+  const int64_t N = z.size(0), C = z.size(1), Co = wt.size(1);
+  sj_sizes(N, C, Co);
+  TORCH_CHECK(Co <= kSiluProjectMaxCo, "silu_project_fwd serves Co <= ", kSiluProjectMaxCo, ", got ", Co);
+  need_aligned16(z, "z");
+  sj_matrix(wt, "wt", C, Co, &z);
+  const float* sc = opt_ptr(scale, Co, "scale", z);
+  const float* sh = opt_ptr(shift, Co, "shift", z);
+  if (present(res)) sj_matrix(*res, "res", N, Co, &z);
+  int64_t B = 1;
+  if (present(apoz)) {
+    need(*apoz, "apoz", 2, &z);
+    B = apoz->size(0);
+    TORCH_CHECK(B > 0 && N % B == 0 && apoz->size(1) == C, "apoz must be (B, ", C, ") with B dividing the ", N,
+                " rows of z, got ", apoz->sizes());
+    need_aligned16(*apoz, "apoz");
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto out = at::empty({N, Co}, z.options());
+  TP_CHECK_HIP(tp_silu_project_fwd(z.data_ptr<float>(), wt.data_ptr<float>(), sc, sh,
+                                   present(res) ? res->data_ptr<float>() : nullptr, out.data_ptr<float>(),
+                                   present(apoz) ? apoz->data_ptr<float>() : nullptr, (int)N, (int)C, (int)Co, (int)B,
+                                   (int)(N / B), cur_stream()));
+  return out;
+}
+
+int64_t silu_project_tay_slots(int64_t HW, int64_t C) {
+  const int64_t lim = int64_t(1) << 29;
+  if (HW < 1 || C < 1 || HW >= lim || C >= lim) return 0;
+  return tp_silu_project_tay_slots((int)HW, (int)C);
+}
+
+// dz (N, C) = (g @ wtT) * silu'(z); tay: a zeroed (silu_project_tay_slots(N / B, C), B, C) slab of partial sums of
+// -(gy * silu(z)) (tay_mode 0) or |gy| (1)
+at::Tensor silu_project_dgrad(const at::Tensor& g, const at::Tensor& z, const at::Tensor& wtT, const OptTensor& tay,
+                              int64_t tay_mode) {
+  need(z, "z", 2);
+  need(wtT, "wtT", 2, &z);
+  const int64_t N = z.size(0), C = z.size(1), Co = wtT.size(0);
+  sj_sizes(N, C, Co);
+  need_aligned16(z, "z");
+  sj_matrix(wtT, "wtT", Co, C, &z);
+  sj_matrix(g, "g", N, Co, &z);
+  int64_t B = 1, R = 0;
+  int mode = 0;
+  if (present(tay)) {
+    mode = tay_mode_arg(tay_mode, 1);
+    need(*tay, "tay", 3, &z);
+    B = tay->size(1);
+    TORCH_CHECK(B > 0 && N % B == 0 && tay->size(2) == C, "tay must be (R, B, ", C, ") with B dividing the ", N,
+                " rows of z, got ", tay->sizes());
+    R = silu_project_tay_slots(N / B, C);
+    TORCH_CHECK(tay->size(0) == R && tay->numel() < (int64_t(1) << 29), "tay must have ", R,
+                " slots (silu_project_tay_slots) and stay below 2^31 bytes, got ", tay->sizes());
+    need_aligned16(*tay, "tay");
+  }
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto dz = at::empty_like(z);
+  TP_CHECK_HIP(tp_silu_project_dgrad(g.data_ptr<float>(), wtT.data_ptr<float>(), z.data_ptr<float>(),
+                                     dz.data_ptr<float>(), present(tay) ? tay->data_ptr<float>() : nullptr, (int)R,
+                                     mode, (int)N, (int)C, (int)Co, (int)B, (int)(N / B), cur_stream()));
+  return dz;
+}
+
 void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv, int64_t row0, int64_t k0,
                      double scale) {
   need(L, "losses");
@@ -914,6 +1001,10 @@ TORCH_LIBRARY(tpamd, m) {
   m.def("prefix_mask(Tensor z, Tensor rank, int p0, int K) -> Tensor");
   m.def("prefix_project(Tensor base, Tensor a, Tensor fill, Tensor wt, Tensor perm, int p0, int cnt) -> Tensor");
   m.def("scaled_project(Tensor a, Tensor sc, Tensor wt, Tensor bias, Tensor? res, int hw) -> Tensor");
+  m.def("silu_project_fwd(Tensor z, Tensor wt, Tensor scale, Tensor shift, Tensor? res=None, Tensor(a!)? apoz=None) "
+        "-> Tensor");
+  m.def("silu_project_dgrad(Tensor g, Tensor z, Tensor wtT, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
+  m.def("silu_project_tay_slots(int HW, int C) -> int", &silu_project_tay_slots);
   m.def("shapley_scatter(Tensor L, Tensor perm, Tensor(a!) sv, int row0, int k0, float scale) -> ()");
   m.def("shapley_column(Tensor L, Tensor perm, Tensor(a!) sv_col, int k0, float scale) -> ()");
   m.def("cross_entropy(Tensor logits, Tensor target, float gscale, bool want_grad) -> (Tensor, Tensor)");
@@ -948,6 +1039,8 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("prefix_mask", &prefix_mask);
   m.impl("prefix_project", &prefix_project);
   m.impl("scaled_project", &scaled_project);
+  m.impl("silu_project_fwd", &silu_project_fwd);
+  m.impl("silu_project_dgrad", &silu_project_dgrad);
   m.impl("shapley_scatter", &shapley_scatter);
   m.impl("shapley_column", &shapley_column);
   m.impl("cross_entropy", &cross_entropy);

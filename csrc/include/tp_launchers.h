@@ -149,6 +149,15 @@ hipError_t tp_prefix_project(const float* base, const float* a, const float* fil
 // C % 4 == 0, Co % 4 == 0, every operand 16-byte aligned)
 hipError_t tp_scaled_project(const float* a, const float* sc, const float* wt, const float* bias, const float* res,
                              float* out, int N, int C, int Co, int B, int HW, int cnt, hipStream_t st);
+// silu_project.hip: out = (silu(z) @ wt) * scale + shift (+ res), apoz (B, C) += [silu(z) > 0]; and
+// dz = (g @ wtT) * silu'(z) with the (R, B, C) score partials of (silu(z), g @ wtT), R = tp_silu_project_tay_slots
+// (z (N, C), wt (C, Co), wtT (Co, C), g / res / out (N, Co); N = B * HW, C % 4 == 0, Co % 4 == 0, forward Co <= 128)
+int tp_silu_project_tay_slots(int HW, int C);
+hipError_t tp_silu_project_fwd(const float* z, const float* wt, const float* scale, const float* shift,
+                               const float* res, float* out, float* apoz, int N, int C, int Co, int B, int HW,
+                               hipStream_t st);
+hipError_t tp_silu_project_dgrad(const float* g, const float* wtT, const float* z, float* dz, float* tay, int R,
+                                 int tay_mode, int N, int C, int Co, int B, int HW, hipStream_t st);
 // prune_ops.hip
 hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx, int nidx, float value,
                            hipStream_t st);

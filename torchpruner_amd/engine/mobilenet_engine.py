@@ -39,7 +39,10 @@ of a gated block are per-(copy, image, channel) scales and biases of ONE hidden 
 EfficientNets (``build_efficientnet_plan`` / ``EfficientNetEngine``, last part of this file) run the
 same way with SiLU units on the LDS-staged depthwise kernels (``tpamd.dwconv_silu_*``,
 csrc/kernels/dwconv_silu.hip), whose forward also leaves the gate's pool partials; APoZ, Taylor and
-Sensitivity only (Shapley stays on the generic path).
+Sensitivity only (Shapley stays on the generic path). The Fused-MBConv blocks of an EfficientNetV2 (dense
+3x3 expand, BN, SiLU, 1x1 project, BN: no depthwise conv, no gate) keep the expand conv's pre-activation
+and run the project conv and its data gradient on the SiLU-on-load GEMM kernels (``tpamd.silu_project_*``,
+csrc/kernels/silu_project.hip).
 """
 from __future__ import annotations
 
@@ -256,6 +259,10 @@ class MobileNetEngine(ResNetEngine):
         return {"w": F.pad(w, (0, 0, 0, 0, 0, 0, 0, cp - c)).contiguous(), "scale": F.pad(scale, (0, cp - c)),
                 "shift": F.pad(shift, (0, cp - c)), "stride": u.conv.stride[0], "pad": u.conv.padding[0]}
 
+    def _pack_block(self, b):
+        return {"expand": self._pack_conv(b.expand) if b.expand is not None else None,
+                "dw": self._pack_dw(b.dw), "project": self._pack_conv(b.project)}
+
     def _pack(self):
         key = self._params_key()
         if key == self._key:
@@ -263,8 +270,7 @@ class MobileNetEngine(ResNetEngine):
         p = self.plan
         blocks = []
         for b in p.blocks:
-            blocks.append({"expand": self._pack_conv(b.expand) if b.expand is not None else None,
-                           "dw": self._pack_dw(b.dw), "project": self._pack_conv(b.project)})
+            blocks.append(self._pack_block(b))
         fc_w = p.fc.weight.detach().float()
         fc_w = F.pad(fc_w, (0, cpad(fc_w.shape[1]) - fc_w.shape[1]))
         fc_b = p.fc.bias.detach().float() if p.fc.bias is not None else torch.zeros(fc_w.shape[0], device=fc_w.device)
@@ -1008,6 +1014,16 @@ EFFNET_SHAPLEY_REASON = ("mobilenet engine: Shapley on an EfficientNet is not lo
 
 
 @dataclass
+class _FusedBlock:
+    """Fused-MBConv: (dense 3x3 conv, BN, SiLU) [, (1x1 conv, BN)]; ``project`` is None at expand ratio 1."""
+    expand: _Unit
+    project: Optional[_Conv]
+    shortcut: bool
+    dw: None = None
+    gate: None = None
+
+
+@dataclass
 class EfficientNetPlan:
     stem: _Unit
     head: _Unit
@@ -1028,6 +1044,42 @@ def _unit_silu(seq, what):
     if type(act) is not nn.SiLU:
         return None, f"{what}: activation {type(act).__name__} is not supported (only SiLU)"
     return _Unit(conv, bn, act), ""
+
+
+def _fused_block(items, blk, what, width):
+    """(_FusedBlock, output width) of a gate-free one- or two-item ``.block``, else (None, reason)."""
+    expand, why = _unit_silu(items[0], f"{what}.block.0 (expand)")
+    if expand is None:
+        return None, why
+    conv = expand.conv
+    if _conv_kind(conv) != "dense" or conv.weight.shape[2] != 3 or conv.stride[0] not in (1, 2) or conv.padding[0] != 1:
+        return None, f"{what}.block.0: the expand conv of a fused block must be a dense 3x3 conv, stride 1 / 2, padding 1"
+    hidden = cout = conv.weight.shape[0]
+    project = None
+    if len(items) == 2:
+        if not isinstance(items[1], nn.Sequential) or len(items[1]) != 2:
+            return None, f"{what}: expected a Fused-MBConv `.block` ((3x3, BN, SiLU), (1x1, BN))"
+        pconv, pbn = items[1]
+        kind = _conv_kind(pconv)
+        if kind != "dense" or not _is_1x1(pconv):
+            return None, f"{what}: the project conv must be a dense 1x1 conv" + ("" if kind == "dense" else f" ({kind})")
+        if not isinstance(pbn, nn.BatchNorm2d) or pbn.running_mean is None:
+            return None, f"{what}: expected a BatchNorm2d with running statistics after the project conv"
+        cout = pconv.weight.shape[0]
+        if pconv.weight.shape[1] != hidden:
+            return None, f"{what}: channel counts of the block's convs do not chain"
+        if cpad(cout) > ops.silu_project.SILU_PROJECT_MAX_CO:
+            return None, f"{what}: the project conv's width exceeds {ops.silu_project.SILU_PROJECT_MAX_CO}"
+        project = _Conv(pconv, pbn)
+    if conv.weight.shape[1] != width:
+        return None, f"{what}: channel counts of the block's convs do not chain"
+    s = conv.stride[0]
+    shortcut = getattr(blk, "use_res_connect", None)
+    if shortcut is None:
+        shortcut = s == 1 and cout == width
+    if shortcut and (s != 1 or cout != width):
+        return None, f"{what}: a shortcut needs stride 1 and equal widths"
+    return _FusedBlock(expand, project, bool(shortcut)), cout
 
 
 def build_efficientnet_plan(model: nn.Module):
@@ -1065,6 +1117,13 @@ def build_efficientnet_plan(model: nn.Module):
         for bi, blk in enumerate(stage):
             what = f"features.{si}.{bi}"
             items = list(blk.block)
+            if len(items) in (1, 2) and not any(is_channel_gate(m) for m in items):  # Fused-MBConv (EfficientNetV2)
+                fused, cout = _fused_block(items, blk, what, width)
+                if fused is None:
+                    return None, cout
+                plan.blocks.append(fused)
+                width = cout
+                continue
             if len(items) not in (3, 4) or not is_channel_gate(items[-2]) or \
                     not isinstance(items[-1], nn.Sequential) or len(items[-1]) != 2:
                 return None, f"{what}: expected an MBConv `.block` {shape}"
@@ -1127,9 +1186,58 @@ def _silu_slope(v: torch.Tensor) -> torch.Tensor:
 class EfficientNetEngine(MobileNetV3Engine):
     # eval_modules (inherited): the SiLU modules after a block's expand conv (where it expands) and
     # after its depthwise conv (before the gate)
+    # Fused-MBConv blocks (``_FusedBlock``: no depthwise unit, no gate) score the SiLU after their expand
+    # conv where they have a project conv; the single-unit block (expand ratio 1) has no hidden point
+    def _all_convs(self):
+        out = [self.plan.stem]
+        for b in self.plan.blocks:
+            out += [c for c in (b.expand, b.dw, b.project) if c is not None]
+        return out + [self.plan.head]
+
+    def eval_modules(self):
+        mods = []
+        for b in self.plan.blocks:
+            if b.dw is None:
+                mods += [b.expand.act] if b.project is not None else []
+            else:
+                mods += ([b.expand.act] if b.expand is not None else []) + [b.dw.act]
+        return mods
+
+    def real_width(self, module) -> int:
+        for b in self.plan.blocks:
+            if b.dw is None:
+                if b.project is not None and module is b.expand.act:
+                    return b.expand.conv.weight.shape[0]
+            elif module is b.dw.act or (b.expand is not None and module is b.expand.act):
+                return b.dw.conv.weight.shape[0]
+        raise KeyError("not a block SiLU of this EfficientNet")
+
+    def _stem_fused(self) -> bool:
+        return self.plan.blocks[0].dw is not None and super()._stem_fused()
+
+    def max_batch(self, sample_shape) -> int:
+        H, W = tuple(sample_shape)[-2:]
+        per = 4 * H * W * 4
+        H, W = _out_hw(self.plan.stem.conv, H, W)
+        per = max(per, 4 * H * W * cpad(self.plan.stem.conv.weight.shape[0]))
+        for b in self.plan.blocks:
+            if b.dw is None:
+                hid = cpad(b.expand.conv.weight.shape[0])
+                H, W = _out_hw(b.expand.conv, H, W)
+                per = max(per, 4 * H * W * hid, 4 * ops.silu_project_tay_slots(H * W, hid) * hid)
+                continue
+            hid = cpad(b.dw.conv.weight.shape[0])
+            per = max(per, 4 * H * W * hid, 4 * ops.dwconv_silu_tay_slots(H, W, hid) * hid)
+            H, W = _out_hw(b.dw.conv, H, W)
+            per = max(per, 4 * H * W * hid, 4 * H * W * cpad(b.project.conv.weight.shape[0]))
+        per = max(per, 4 * H * W * cpad(self.plan.head.conv.weight.shape[0]))
+        return max(1, ((1 << 31) - 1) // per)
+
     def _params_key(self):
         key = list(ResNetEngine._params_key(self))
         for b in self.plan.blocks:
+            if b.gate is None:
+                continue
             for t in (b.gate.fc1.weight, b.gate.fc1.bias, b.gate.fc2.weight, b.gate.fc2.bias):
                 if t is not None:
                     key.append((t.data_ptr(), t._version, tuple(t.shape)))
@@ -1141,21 +1249,27 @@ class EfficientNetEngine(MobileNetV3Engine):
         q["code"] = _se_codes(gate)[0]
         return q
 
-    def _pack(self):
-        key = self._params_key()
-        if key == self._key:
-            return self._packed
-        gates = [self._pack_gate(b.gate) for b in self.plan.blocks]
-        P = MobileNetEngine._pack(self)  # convs, depthwise units and the single classifier Linear
-        for e, q in zip(P["blocks"], gates):
-            e["gate"] = q
-        return P
+    def _pack_block(self, b):
+        if b.dw is not None:
+            e = MobileNetEngine._pack_block(self, b)
+            e["gate"] = self._pack_gate(b.gate)
+            return e
+        q = None
+        if b.project is not None:
+            q = self._pack_conv(b.project)  # w: (Co padded, C padded), unscaled
+            q["wt_fwd"] = q["w"].t().contiguous()                       # silu_project_fwd's (C, Co)
+            q["wT_bwd"] = (q["w"] * q["scale"][:, None]).contiguous()   # silu_project_dgrad's (Co, C), BN scale folded
+        return {"expand": self._pack_conv(b.expand), "project": q}
+
+    _pack = MobileNetEngine._pack  # convs, depthwise units, gates (``_pack_block``) and the single classifier Linear
 
     # ------------------------------------------------------------------ forward
     def _block(self, T, blk, e, h, in_act, apoz=None, saved=None):
         """One MBConv block from its (linear, or for a fused stem pre-activation) input ``h``; appends
         (input, z, y, input activation code, pre-activation of y, gate state) to ``saved``."""
         apoz = apoz or {}
+        if blk.dw is None:
+            return self._fused_block(T, blk, e, h, apoz, saved)
         if blk.expand is not None:
             z = self._conv(T, e["expand"], h, False, apoz=apoz.get(blk.expand.act))
             in_act = _SILU
@@ -1175,6 +1289,47 @@ class EfficientNetEngine(MobileNetV3Engine):
         if saved is not None:
             saved.append((h, z, y, in_act, pre, (hh, z1, sg)))
         return out
+
+    def _fused_block(self, T, blk, e, h, apoz, saved):
+        """A Fused-MBConv block from its (linear) input: the 3x3 expand conv stores its pre-activation z
+        and the project GEMM applies the SiLU as it loads it (``tpamd.silu_project_fwd``: shortcut and the
+        SiLU's APoZ counts in the same pass); appends (input, z) to ``saved``."""
+        z = self._conv(T, e["expand"], h, False)
+        if blk.project is None:  # expand ratio 1: the unit is the block
+            out = F.silu(z)
+            if blk.shortcut:
+                out += h
+        else:
+            q = e["project"]
+            B, H, W, C = z.shape
+            co = q["scale"].numel()
+            out = T.silu_project_fwd(z.view(-1, C), q["wt_fwd"], q["scale"], q["shift"],
+                                     h.view(-1, co) if blk.shortcut else None, apoz.get(blk.expand.act)).view(B, H, W, co)
+        if saved is not None:
+            saved.append((h, z))
+        return out
+
+    def _fused_block_bwd(self, T, blk, e, sv, g, want, mode, arena, raw_slabs, out, stop):
+        """dL/d(block input) from g = dL/d(block output) (None when ``stop``); the expand SiLU's score
+        partials come from the project dgrad's epilogue (``tpamd.silu_project_dgrad``)."""
+        h, z = sv
+        B, H, W, C = z.shape
+        if blk.project is None:
+            dz = (g * _silu_slope(z)).contiguous()
+        else:
+            wanted = blk.expand.act in want
+            tay = self._slab(arena, T.silu_project_tay_slots(H * W, C), B, C, z.device) if wanted else None
+            dz = T.silu_project_dgrad(g.view(-1, g.shape[3]), z.view(-1, C), e["project"]["wT_bwd"], tay,
+                                      _TAY_MODES[mode]).view(B, H, W, C)
+            if wanted:
+                if raw_slabs:
+                    out[blk.expand.act] = tay
+                else:
+                    sums = tay.sum(0)
+                    out[blk.expand.act] = sums.abs_() if mode == "taylor" else sums
+        if stop:
+            return None
+        return self._dgrad(T, e["expand"], dz, None, res=g if blk.shortcut else None, in_hw=tuple(h.shape[1:3]))[0]
 
     def _stem_out(self, T, P, x):
         h = T.nchw_to_nhwc_pad(x.float().contiguous(), 4)
@@ -1198,8 +1353,8 @@ class EfficientNetEngine(MobileNetV3Engine):
         zh, _, _ = saved.pop()
         B = logits.shape[0]
         blocks = self.plan.blocks
-        first = min((bi for bi, b in enumerate(blocks)
-                     if b.dw.act in want or (b.expand is not None and b.expand.act in want)), default=None)
+        first = min((bi for bi, b in enumerate(blocks) if (b.dw is not None and b.dw.act in want) or
+                     (b.expand is not None and b.expand.act in want)), default=None)
         out = {}
         if first is None:
             return out
@@ -1214,6 +1369,9 @@ class EfficientNetEngine(MobileNetV3Engine):
         arena = [torch.zeros(size, device=x.device) if size else None, 0, 0]
         for bi in range(len(blocks) - 1, first - 1, -1):
             blk, e = blocks[bi], P["blocks"][bi]
+            if blk.dw is None:
+                g = self._fused_block_bwd(T, blk, e, saved[bi], g, want, mode, arena, raw_slabs, out, bi == first)
+                continue
             h, z, yd, in_act, pre, (hh, z1, sg) = saved[bi]
             q = e["gate"]
             gy, _ = self._dgrad(T, e["project"], g, None)  # dL/d(project input), unfactored

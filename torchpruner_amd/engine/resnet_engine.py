@@ -409,7 +409,7 @@ class ResNetEngine:
             return buf[off:off + n].view(R, B, N)
         return torch.zeros(R, B, N, device=dev)
 
-    def _dgrad(self, T, e, g, mask, res=None, res_stride=1, low_res=False, tay_mode=None, arena=None):
+    def _dgrad(self, T, e, g, mask, res=None, res_stride=1, low_res=False, tay_mode=None, arena=None, in_hw=None):
         """dL/d(input) of conv ``e`` from g = dL/d(conv output) (BN scale folded in), plus
         ``res``, masked by ``mask`` (the input's post-ReLU activation). ``low_res``: a strided
         1x1 conv's gradient at the output resolution (scattered by the consumer's res_stride).
@@ -425,7 +425,7 @@ class ResNetEngine:
         ks, s = e["ks"], e["stride"]
         N = e["wt"].shape[0]
         transposed = s > 1 and not low_res
-        Ho, Wo = (mask.shape[1], mask.shape[2]) if transposed else (H, W)
+        Ho, Wo = (in_hw or (mask.shape[1], mask.shape[2])) if transposed else (H, W)  # in_hw: a strided conv, no mask
         M, K = B * Ho * Wo, e["wt"].shape[1]
         pad = e["pad"] if (transposed or ks == 3) else 0
         if transposed:

@@ -5,12 +5,14 @@ from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet34, resnet50
 from .mlp import FCNet, FMNISTConvNet, cifar10_fc, mnist_fc
 from .mobilenet import InvertedResidual, MobileNetV2, mobilenet_v2
 from .mobilenet_v3 import InvertedResidualV3, MobileNetV3, SqueezeExcitation, mobilenet_v3_large, mobilenet_v3_small
-from .efficientnet import EfficientNet, MBConv, StochasticDepth, efficientnet, efficientnet_b0
+from .efficientnet import (EfficientNet, FusedMBConv, MBConv, StochasticDepth, efficientnet, efficientnet_b0,
+                           efficientnet_v2, efficientnet_v2_s)
 
 __all__ = [
     "InvertedResidual", "MobileNetV2", "mobilenet_v2",
     "InvertedResidualV3", "MobileNetV3", "SqueezeExcitation", "mobilenet_v3_large", "mobilenet_v3_small",
     "EfficientNet", "MBConv", "StochasticDepth", "efficientnet", "efficientnet_b0",
+    "FusedMBConv", "efficientnet_v2", "efficientnet_v2_s",
     "PartialForwardMixin", "SequentialPartial", "run_stages", "with_forward_partial",
     "VGG", "get_vgg_model_with_name", "make_features", "prunable_vgg16", "vgg_cifar",
     "ResNet", "BasicBlock", "Bottleneck", "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",

@@ -176,13 +176,19 @@ def get_mobilenet_pruning_graph(model: nn.Module):
 def _v3_block_entry(block):
     """The graph entry of a MobileNetV3-style block (torchvision's layout: ``block.block`` is a
     Sequential of ``[expand unit,] depthwise unit, [gate,] project unit``, every unit a Sequential
-    that starts with ``Conv2d, BatchNorm``), or None (no expansion, or another layout)."""
+    that starts with ``Conv2d, BatchNorm``), or None (no expansion, or another layout). A gate-free block of
+    two units whose convs are dense (a Fused-MBConv) gives ``(expand conv, [BN, project conv])``."""
     seq = getattr(block, "block", None)
     if not isinstance(seq, nn.Sequential):
         return None
     mods = list(seq)
     gates = [m for m in mods if is_channel_gate(m)]
     units = [m for m in mods if not is_channel_gate(m)]
+    if len(units) == 2 and not gates:  # Fused-MBConv (EfficientNetV2): dense expand unit, project unit
+        if all(isinstance(u, nn.Sequential) and len(u) >= 2 and isinstance(u[0], nn.Conv2d)
+               and isinstance(u[1], _BatchNorm) and u[0].groups == 1 for u in units):
+            return units[0][0], [units[0][1], units[1][0]]
+        return None
     if len(units) != 3 or len(gates) > 1 or (gates and mods[2] is not gates[0]):
         return None
     if not all(isinstance(u, nn.Sequential) and len(u) >= 2 and isinstance(u[0], nn.Conv2d)
