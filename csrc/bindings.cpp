@@ -374,6 +374,38 @@ at::Tensor silu_project_dgrad(const at::Tensor& g, const at::Tensor& z, const at
   return dz;
 }
 
+// out[j] = sum_c [rank[c] >= p0 + j] silu(z[:, c]) (x) wt[c, :] + shift (+ res), j < cnt: the cnt stacked outputs of a
+// Fused-MBConv project conv whose input copies mask one more channel of silu(z) each
+// (csrc/kernels/silu_prefix_project.hip)
+at::Tensor silu_prefix_project(const at::Tensor& z, const at::Tensor& wt, const at::Tensor& shift, const OptTensor& res,
+                               const at::Tensor& perm, const at::Tensor& rank, int64_t p0, int64_t cnt) {
+  need(z, "z", 2);
+  need(wt, "wt", 2, &z);
+  const int64_t N = z.size(0), C = z.size(1), Co = wt.size(1);
+  sj_sizes(N, C, Co);
+  TORCH_CHECK(Co <= kSiluProjectMaxCo, "silu_prefix_project serves Co <= ", kSiluProjectMaxCo, ", got ", Co);
+  need_aligned16(z, "z");
+  sj_matrix(wt, "wt", C, Co, &z);
+  const float* sh = opt_ptr(shift, Co, "shift", z);
+  if (present(res)) sj_matrix(*res, "res", N, Co, &z);
+  for (const at::Tensor* t : {&perm, &rank})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->device() == z.device() && t->dim() == 1 &&
+                    t->is_contiguous(), "perm and rank must be contiguous int32 vectors on the device of z");
+  const int64_t n = perm.numel();
+  TORCH_CHECK(rank.numel() == C, "rank must have ", C, " elements, got ", rank.numel());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rank.data_ptr()) % 16 == 0, "rank must be 16-byte aligned");
+  TORCH_CHECK(n <= C && cnt >= 1 && p0 >= 0 && p0 + cnt - 1 <= n, "bad prefix range (p0 ", p0, ", cnt ", cnt, ", n ", n,
+              ", C ", C, ")");
+  TORCH_CHECK(N * Co * cnt < (int64_t(1) << 29), "silu_prefix_project operands must stay below 2^31 bytes");
+  at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(z.device());
+  auto out = at::empty({cnt, N, Co}, z.options());
+  TP_CHECK_HIP(tp_silu_prefix_project(z.data_ptr<float>(), wt.data_ptr<float>(), sh,
+                                      present(res) ? res->data_ptr<float>() : nullptr, perm.data_ptr<int>(),
+                                      rank.data_ptr<int>(), out.data_ptr<float>(), (int)N, (int)C, (int)Co, (int)n,
+                                      (int)p0, (int)cnt, cur_stream()));
+  return out;
+}
+
 void shapley_scatter(const at::Tensor& L, const at::Tensor& perm, at::Tensor& sv, int64_t row0, int64_t k0,
                      double scale) {
   need(L, "losses");
@@ -1005,6 +1037,8 @@ TORCH_LIBRARY(tpamd, m) {
         "-> Tensor");
   m.def("silu_project_dgrad(Tensor g, Tensor z, Tensor wtT, Tensor(a!)? tay=None, int tay_mode=0) -> Tensor");
   m.def("silu_project_tay_slots(int HW, int C) -> int", &silu_project_tay_slots);
+  m.def("silu_prefix_project(Tensor z, Tensor wt, Tensor shift, Tensor? res, Tensor perm, Tensor rank, int p0, int cnt) "
+        "-> Tensor");
   m.def("shapley_scatter(Tensor L, Tensor perm, Tensor(a!) sv, int row0, int k0, float scale) -> ()");
   m.def("shapley_column(Tensor L, Tensor perm, Tensor(a!) sv_col, int k0, float scale) -> ()");
   m.def("cross_entropy(Tensor logits, Tensor target, float gscale, bool want_grad) -> (Tensor, Tensor)");
@@ -1041,6 +1075,7 @@ TORCH_LIBRARY_IMPL(tpamd, CUDA, m) {
   m.impl("scaled_project", &scaled_project);
   m.impl("silu_project_fwd", &silu_project_fwd);
   m.impl("silu_project_dgrad", &silu_project_dgrad);
+  m.impl("silu_prefix_project", &silu_prefix_project);
   m.impl("shapley_scatter", &shapley_scatter);
   m.impl("shapley_column", &shapley_column);
   m.impl("cross_entropy", &cross_entropy);

@@ -158,6 +158,12 @@ hipError_t tp_silu_project_fwd(const float* z, const float* wt, const float* sca
                                hipStream_t st);
 hipError_t tp_silu_project_dgrad(const float* g, const float* wtT, const float* z, float* dz, float* tay, int R,
                                  int tay_mode, int N, int C, int Co, int B, int HW, hipStream_t st);
+// silu_prefix_project.hip: out[j, n, :] = sum_c [rank[c] >= p0 + j] silu(z[n, c]) wt[c, :] + shift (+ res[n, :])
+// (z (N, C), wt (C, Co), shift (Co), res (N, Co) or null, perm (n <= C) the permutation, rank (C) its ranks over
+// the padded width, out (cnt, N, Co); C % 4 == 0, Co % 4 == 0, Co <= 128, p0 + cnt - 1 <= n)
+hipError_t tp_silu_prefix_project(const float* z, const float* wt, const float* shift, const float* res,
+                                  const int* perm, const int* rank, float* out, int N, int C, int Co, int n, int p0,
+                                  int cnt, hipStream_t st);
 // prune_ops.hip
 hipError_t tp_channel_fill(float* x, long long B, int C, long long S, const int64_t* idx, int nidx, float value,
                            hipStream_t st);

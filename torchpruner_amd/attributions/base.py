@@ -159,7 +159,8 @@ class _AttributionMetric(ABC):
             "compute_dtype must be None, torch.float32, torch.bfloat16 or torch.float16"
         self.compute_dtype = compute_dtype
         # MobileNet engine (engine/mobilenet_engine.py): opt-in. None reads TORCHPRUNER_MOBILENET_ENGINE
-        # (default 0); APoZ / Taylor / Sensitivity / Shapley then try fused -> resnet -> mobilenet -> generic
+        # (default 0); APoZ / Taylor / Sensitivity / Shapley then try fused -> resnet -> mobilenet -> generic.
+        # "shapley" is True plus Shapley on the engine for EfficientNets (True alone leaves that generic)
         self.mobilenet_engine = mobilenet_engine
         self._ckpt = None
         self._run_accs = None
@@ -569,14 +570,17 @@ class _AttributionMetric(ABC):
         ``TORCHPRUNER_MOBILENET_ENGINE``) and serves ``eval_modules`` (eval-mode torchvision-layout
         MobileNetV2, block ReLU6s, or MobileNetV3, block ReLUs / Hardswishes, the latter not for
         ``shapley``; any differentiable criterion), else None. Switched off, it leaves no rejection
-        reason: the path is then exactly the one without it."""
+        reason: the path is then exactly the one without it. An EfficientNet's Shapley runs on the
+        engine only when the option's value is ``"shapley"``."""
         from ..engine.fused_chain import _reject
         from ..engine.mobilenet_engine import maybe_mobilenet_engine, mobilenet_engine_default
-        on = mobilenet_engine_default() if self.mobilenet_engine is None else bool(self.mobilenet_engine)
+        on = mobilenet_engine_default() if self.mobilenet_engine is None else self.mobilenet_engine
         if not on:
             return None
         if not self._engines_allowed():
             return _reject(why, f"compute_dtype={self.compute_dtype} runs the generic autocast path")
+        if shapley and on == "shapley":  # an EfficientNet's prefixes on the engine too
+            shapley = "lower"
         return maybe_mobilenet_engine(self.model, eval_modules, self.device, grad=grad, why=why, shapley=shapley)
 
     def _fused_engine(self, eval_modules, why=None, need_ce=True, pre_act_ok=False):

@@ -362,11 +362,13 @@ class ShapleyAttributionMetric(_AttributionMetric):
         batch; the K stacked outputs of the block's linear project conv come from one conv of the
         base prefix and a running rank-1 subtraction per pixel (``ops.prefix_project``), or behind a
         MobileNetV3 gate from the channel-scaled project GEMM (``ops.scaled_project``: per-copy
-        scales and biases of the one hidden activation). Either way the K masked copies of the 4-6x
-        wider hidden activation are never built, and the outputs go through the rest of the network
-        in ONE engine forward."""
+        scales and biases of the one hidden activation), or at the expand SiLU of an EfficientNetV2
+        Fused-MBConv block from the SiLU prefix-scan project GEMM (``ops.silu_prefix_project``, with
+        ``mobilenet_engine="shapley"``). Either way the K masked copies of the 4-6x wider hidden
+        activation are never built, and the outputs go through the rest of the network in ONE engine
+        forward."""
         from ...engine.fused_chain import engine_criterion, per_sample_loss
-        eng = self._mobilenet_engine([module], why, shapley=True)  # V2 and V3 layouts
+        eng = self._mobilenet_engine([module], why, shapley=True)  # V2 and V3 layouts; EfficientNets by opt-in
         if eng is None:
             return None
         crit = engine_criterion(self.criterion, self.device)  # None: the fused cross-entropy kernel

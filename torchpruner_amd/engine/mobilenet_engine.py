@@ -38,11 +38,15 @@ of a gated block are per-(copy, image, channel) scales and biases of ONE hidden 
 
 EfficientNets (``build_efficientnet_plan`` / ``EfficientNetEngine``, last part of this file) run the
 same way with SiLU units on the LDS-staged depthwise kernels (``tpamd.dwconv_silu_*``,
-csrc/kernels/dwconv_silu.hip), whose forward also leaves the gate's pool partials; APoZ, Taylor and
-Sensitivity only (Shapley stays on the generic path). The Fused-MBConv blocks of an EfficientNetV2 (dense
-3x3 expand, BN, SiLU, 1x1 project, BN: no depthwise conv, no gate) keep the expand conv's pre-activation
-and run the project conv and its data gradient on the SiLU-on-load GEMM kernels (``tpamd.silu_project_*``,
-csrc/kernels/silu_project.hip).
+csrc/kernels/dwconv_silu.hip), whose forward also leaves the gate's pool partials. The Fused-MBConv blocks
+of an EfficientNetV2 (dense 3x3 expand, BN, SiLU, 1x1 project, BN: no depthwise conv, no gate) keep the
+expand conv's pre-activation and run the project conv and its data gradient on the SiLU-on-load GEMM
+kernels (``tpamd.silu_project_*``, csrc/kernels/silu_project.hip). APoZ, Taylor and Sensitivity run there
+whenever the engine is on; Shapley only with the ``"shapley"`` value of the option (``mobilenet_engine=
+"shapley"`` / ``TORCHPRUNER_MOBILENET_ENGINE=shapley``; plain ``True`` keeps it on the generic path): an
+MBConv block's prefixes then take the MobileNetV3 gated route with the gate's inner SiLU, a fused block's
+the SiLU prefix-scan project GEMM (``ops.silu_prefix_project``, csrc/kernels/silu_prefix_project.hip), which
+writes the K stacked block outputs from the stored pre-activation in one launch.
 """
 from __future__ import annotations
 
@@ -664,19 +668,23 @@ def _hs_slope(v: torch.Tensor) -> torch.Tensor:
     return torch.where(v < -3.0, torch.zeros_like(v), torch.where(v <= 3.0, v / 3.0 + 0.5, torch.ones_like(v)))
 
 
-def _gated_operands(rank_t, p0, cnt, pool, fill, q, wt, shift):
+def _gated_operands(rank_t, p0, cnt, pool, fill, q, wt, shift, inner=None):
     """(sc (cnt, B, C), bias (cnt, B, Co)) of ``ops.scaled_project`` for the prefixes p0 .. p0+cnt-1 of
     a gated block: copy j masks the channels of rank < p0 + j. ``pool`` (B, C): the unmasked
     activation's spatial mean; ``fill`` (C,): the value of a masked channel; ``q``: the gate pack
-    (w1, b1, w2, b2, code); ``wt`` (C, Co), ``shift`` (Co,): the folded project conv. The mask is
-    folded into both: a masked channel has scale 0 and adds fill * gate to the bias product, which
-    runs on the same GEMM (one row per copy and image)."""
+    (w1, b1, w2, b2, code); ``wt`` (C, Co), ``shift`` (Co,): the folded project conv; ``inner``: the
+    activation code inside the gate (``ops.se_gate_act_fwd``; None: the ReLU of ``ops.se_gate_fwd``). The
+    mask is folded into both: a masked channel has scale 0 and adds fill * gate to the bias product,
+    which runs on the same GEMM (one row per copy and image)."""
     B, C = pool.shape
     lim = torch.arange(p0, p0 + cnt, device=pool.device, dtype=rank_t.dtype).view(cnt, 1, 1)
     masked = (rank_t.view(1, 1, C) < lim).expand(cnt, B, C)
     zero = torch.zeros((), dtype=pool.dtype, device=pool.device)
-    p = torch.where(masked, fill, pool.unsqueeze(0))
-    _, s = ops.se_gate_fwd(p.reshape(cnt * B, C), q["w1"], q["b1"], q["w2"], q["b2"], q["code"])
+    p = torch.where(masked, fill, pool.unsqueeze(0)).reshape(cnt * B, C)
+    if inner is None:
+        _, s = ops.se_gate_fwd(p, q["w1"], q["b1"], q["w2"], q["b2"], q["code"])
+    else:
+        _, _, s = ops.se_gate_act_fwd(p, q["w1"], q["b1"], q["w2"], q["b2"], q["code"], inner)
     sc = torch.where(masked, zero, s.view(cnt, B, C))
     fsc = torch.where(masked, fill, zero).reshape(1, cnt * B, C)
     bias = ops.scaled_project(s, fsc, wt, shift.expand(1, cnt * B, shift.numel()).contiguous(), None, 1)
@@ -685,6 +693,7 @@ def _gated_operands(rank_t, p0, cnt, pool, fill, q, wt, shift):
 
 class MobileNetV3Engine(MobileNetEngine):
     _pooled = None  # (y, se_pool(y)) of the last forward_to on a gated block
+    _gate_inner = None  # activation code inside the gates (``_gated_operands``); None: ReLU
 
     def eval_modules(self):
         """The ReLU / Hardswish modules the engine scores: per block the post-expand one (where the
@@ -974,7 +983,8 @@ class MobileNetV3Engine(MobileNetEngine):
         co = e["project"]["scale"].numel()
         if self._use_scaled_project():
             pe = self._bwd_operands(e["project"])  # wt: (C, Cout) with the BN scale folded in
-            sc, bias = _gated_operands(rank_t, p0, cnt, self._pool_of(y), fill, e["gate"], pe["wt"], pe["shift"])
+            sc, bias = _gated_operands(rank_t, p0, cnt, self._pool_of(y), fill, e["gate"], pe["wt"], pe["shift"],
+                                       self._gate_inner)
             out = ops.scaled_project(y.view(B * Ho * Wo, C), sc, pe["wt"], bias,
                                      None if res is None else res.view(B * Ho * Wo, co), Ho * Wo)
             return out.view(cnt * B, Ho, Wo, co)
@@ -1007,10 +1017,12 @@ class MobileNetV3Engine(MobileNetEngine):
 # (``ops.se_gate_act_*``, inner code 1) and the classifier is one Linear. The depthwise unit runs the
 # LDS-staged kernels of dwconv_silu.hip (``tpamd.dwconv_silu_*``): the forward stores the
 # pre-activation for the backward and the per-block sums of its output, which are the gate's pooled
-# mean (no ``se_pool`` pass over the activation it just wrote). Taylor, Sensitivity and APoZ only.
+# mean (no ``se_pool`` pass over the activation it just wrote). APoZ, Taylor and Sensitivity by default;
+# Shapley prefixes by opt-in (see "partial forward" in the engine class).
 _SILU = 4
-EFFNET_SHAPLEY_REASON = ("mobilenet engine: Shapley on an EfficientNet is not lowered (the engine serves APoZ, Taylor "
-                         "and Sensitivity there); the generic path evaluates its prefixes")
+EFFNET_SHAPLEY_REASON = ("mobilenet engine: Shapley on an EfficientNet runs on the engine only by opt-in "
+                         "(mobilenet_engine=\"shapley\" or TORCHPRUNER_MOBILENET_ENGINE=shapley); the generic path "
+                         "evaluates its prefixes")
 
 
 @dataclass
@@ -1259,6 +1271,7 @@ class EfficientNetEngine(MobileNetV3Engine):
             q = self._pack_conv(b.project)  # w: (Co padded, C padded), unscaled
             q["wt_fwd"] = q["w"].t().contiguous()                       # silu_project_fwd's (C, Co)
             q["wT_bwd"] = (q["w"] * q["scale"][:, None]).contiguous()   # silu_project_dgrad's (Co, C), BN scale folded
+            q["wt_pfx"] = q["wT_bwd"].t().contiguous()                  # silu_prefix_project's (C, Co), BN scale folded
         return {"expand": self._pack_conv(b.expand), "project": q}
 
     _pack = MobileNetEngine._pack  # convs, depthwise units, gates (``_pack_block``) and the single classifier Linear
@@ -1403,17 +1416,147 @@ class EfficientNetEngine(MobileNetV3Engine):
             self._arena_sizes[akey] = arena[2]
         return out
 
-    # ------------------------------------------------------------------ Shapley: not lowered
+    # ------------------------------------------------------------------ partial forward (Shapley; opt-in)
+    # An MBConv block takes the MobileNetV3 gated route (``prefix_project_out`` on ``ops.scaled_project``)
+    # with SiLU fills, the gate's inner SiLU (``_gate_inner``) and the pooled mean the depthwise kernel's
+    # pool slab already holds. A Fused-MBConv block with a project conv is evaluated at its expand SiLU from
+    # the stored pre-activation z: copy j is the project conv of silu(z) with the channels of rank < p0 + j
+    # zeroed, and ``ops.silu_prefix_project`` writes the cnt stacked outputs in one launch (a masked GEMM,
+    # then a rank-1 subtraction per further copy on the accumulators in registers).
+    _gate_inner = 1
+
+    def locate(self, module):
+        for bi, b in enumerate(self.plan.blocks):
+            if b.dw is None:
+                if b.project is not None and module is b.expand.act:
+                    return bi, "expand"
+            elif module is b.dw.act:
+                return bi, "dw"
+            elif b.expand is not None and module is b.expand.act:
+                return bi, "expand"
+        raise KeyError("not a block SiLU (after an expand or depthwise conv) of this EfficientNet")
+
     def forward_to(self, x: torch.Tensor, bi: int):
-        raise NotImplementedError(EFFNET_SHAPLEY_REASON)
+        """(block ``bi``'s input h, its post-depthwise SiLU output y before the gate, or for a Fused-MBConv
+        block its expand conv's pre-activation z), in engine layout; an MBConv block's pooled mean of y is
+        kept from the depthwise kernel's pool slab for :meth:`prefix_logits`."""
+        T = ops.require()
+        P = self._pack()
+        h, _, in_act = self._stem_out(T, P, x)
+        for b in range(bi):
+            h = self._block(T, self.plan.blocks[b], P["blocks"][b], h, in_act)
+            in_act = 0
+        blk, e = self.plan.blocks[bi], P["blocks"][bi]
+        self._pooled = None
+        if blk.dw is None:
+            return h, self._conv(T, e["expand"], h, False)
+        if blk.expand is not None:
+            z, in_act = self._conv(T, e["expand"], h, False), _SILU
+        else:
+            z = h
+        d = e["dw"]
+        B, H, W, C = z.shape
+        Ho, Wo = _out_hw(blk.dw.conv, H, W)
+        pool = z.new_zeros(T.dwconv_silu_pool_slots(Ho, Wo, C), B, C)
+        y = T.dwconv_silu_fwd(z, d["w"], d["scale"], d["shift"], d["stride"], d["pad"], in_act, _SILU, None, None, pool)
+        self._pooled = (y, (pool[0] if pool.shape[0] == 1 else pool.sum(0)).div_(Ho * Wo))
+        return h, y
+
+    def prefix_fill(self, bi: int, kind: str) -> torch.Tensor:
+        """(C_padded,) value a masked channel of an MBConv block's post-depthwise output takes: zeros for
+        ``"dw"``, SiLU of the folded depthwise BN shift for ``"expand"``."""
+        d = self._pack()["blocks"][bi]["dw"]
+        key = "fill_" + kind
+        if key not in d:
+            d[key] = torch.zeros_like(d["shift"]) if kind == "dw" else F.silu(d["shift"]).contiguous()
+        return d[key]
+
+    @staticmethod
+    def _widths(b):
+        """(conv that sets the block's output map, padded hidden width, padded output width)"""
+        if b.dw is None:
+            hid = cpad(b.expand.conv.weight.shape[0])
+            return b.expand.conv, hid, hid if b.project is None else cpad(b.project.conv.weight.shape[0])
+        return b.dw.conv, cpad(b.dw.conv.weight.shape[0]), cpad(b.project.conv.weight.shape[0])
+
+    def _tail_elems(self, bi: int, H: int, W: int) -> int:
+        per = H * W * self._widths(self.plan.blocks[bi])[2]
+        for b in self.plan.blocks[bi + 1:]:
+            conv, hid, out = self._widths(b)
+            if b.dw is not None:  # the expand output, at the input's resolution
+                per = max(per, H * W * hid)
+            H, W = _out_hw(conv, H, W)
+            per = max(per, H * W * hid, H * W * out)
+        return max(per, H * W * cpad(self.plan.head.conv.weight.shape[0]))
+
+    def downstream_elems(self, bi: int, sample_shape) -> int:
+        H, W = _out_hw(self.plan.stem.conv, *tuple(sample_shape)[-2:])
+        for b in self.plan.blocks[:bi + 1]:
+            H, W = _out_hw(self._widths(b)[0], H, W)
+        return self._tail_elems(bi, H, W)
+
+    def _block_tail(self, T, blk, e, y, res):
+        q = e["gate"]
+        _, _, sg = ops.se_gate_act_fwd(self._pool_of(y), q["w1"], q["b1"], q["w2"], q["b2"], q["code"], 1)
+        return self._conv(T, e["project"], ops.se_scale(y, sg), False, res=res)
+
+    def block_logits(self, bi: int, h: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        blk, e = self.plan.blocks[bi], self._pack()["blocks"][bi]
+        if blk.dw is not None:
+            return super().block_logits(bi, h, y)
+        q = e["project"]
+        B, H, W, C = y.shape
+        co = q["scale"].numel()
+        out = ops.require().silu_project_fwd(y.view(-1, C), q["wt_fwd"], q["scale"], q["shift"],
+                                             h.view(-1, co) if blk.shortcut else None, None)
+        return self.logits_from(bi, out.view(B, H, W, co))
+
+    def prefix_logits(self, bi: int, kind: str, h: torch.Tensor, y: torch.Tensor, perm_t: torch.Tensor,
+                      rank_t: torch.Tensor, p0: int, cnt: int) -> torch.Tensor:
+        """As :meth:`MobileNetEngine.prefix_logits`. An MBConv block takes the gated route
+        (:meth:`prefix_project_out`); at a Fused-MBConv block ``y`` is the pre-activation z of
+        :meth:`forward_to` and the stacked outputs come from ``ops.silu_prefix_project``, or with
+        ``TORCHPRUNER_PREFIX_DELTA=0`` from the project conv on the cnt masked copies of silu(z)."""
+        if self.plan.blocks[bi].dw is not None:
+            return super().prefix_logits(bi, kind, h, y, perm_t, rank_t, p0, cnt)
+        B, H, W, C = y.shape
+        co = self._pack()["blocks"][bi]["project"]["scale"].numel()
+        delta = os.environ.get("TORCHPRUNER_PREFIX_DELTA", "1") != "0"
+        # copies per piece: the stacked project output (and, without the delta, input) below 2^31 bytes
+        piece = max(1, ((1 << 31) - 1) // (4 * B * H * W * (co if delta else max(co, C))))
+        if cnt > piece:
+            return torch.cat([self.prefix_logits(bi, kind, h, y, perm_t, rank_t, p0 + j, min(piece, cnt - j))
+                              for j in range(0, cnt, piece)], 0)
+        return self.logits_from(bi, self.fused_prefix_out(bi, h, y, perm_t, rank_t, p0, cnt, delta))
+
+    def fused_prefix_out(self, bi: int, h: torch.Tensor, z: torch.Tensor, perm_t: torch.Tensor, rank_t: torch.Tensor,
+                         p0: int, cnt: int, delta: bool = True) -> torch.Tensor:
+        """The project stage of :meth:`prefix_logits` on a Fused-MBConv block: the (cnt * B, H, W, Co) stacked
+        block outputs from ``ops.silu_prefix_project``, or without ``delta`` from the project conv on the cnt
+        masked copies of silu(z)."""
+        blk, q = self.plan.blocks[bi], self._pack()["blocks"][bi]["project"]
+        B, H, W, C = z.shape
+        co = q["scale"].numel()
+        res = h if blk.shortcut else None
+        if delta:
+            out = ops.silu_prefix_project(z.view(-1, C), q["wt_pfx"], q["shift"],
+                                          None if res is None else res.view(-1, co), perm_t, rank_t, p0, cnt)
+            return out.view(cnt * B, H, W, co)
+        lim = torch.arange(p0, p0 + cnt, device=z.device, dtype=rank_t.dtype).view(cnt, 1, 1, 1, 1)
+        a = torch.where(rank_t.view(1, 1, 1, 1, C) < lim, torch.zeros((), device=z.device), F.silu(z).unsqueeze(0))
+        if res is not None and cnt > 1:
+            res = res.repeat(cnt, 1, 1, 1)
+        return self._conv(ops.require(), q, a.view(cnt * B, H, W, C), False, res=res)
 
 
 _ENGINES: "weakref.WeakKeyDictionary[nn.Module, MobileNetEngine]" = weakref.WeakKeyDictionary()
 
 
-def mobilenet_engine_default() -> bool:
-    """``TORCHPRUNER_MOBILENET_ENGINE`` (default 0: the engine is opt-in)."""
-    return os.environ.get("TORCHPRUNER_MOBILENET_ENGINE", "0") not in ("0", "")
+def mobilenet_engine_default():
+    """``TORCHPRUNER_MOBILENET_ENGINE`` (default 0: the engine is opt-in): False, True, or "shapley" (on, and
+    an EfficientNet's Shapley prefixes run on the engine too: ``maybe_mobilenet_engine(shapley="lower")``)."""
+    v = os.environ.get("TORCHPRUNER_MOBILENET_ENGINE", "0")
+    return "shapley" if v == "shapley" else v not in ("0", "")
 
 
 def _engine_sig(eng):
@@ -1424,10 +1567,11 @@ def _engine_sig(eng):
 def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, shapley=False):
     """A MobileNetEngine (MobileNetV2 layout), MobileNetV3Engine or EfficientNetEngine (tried in this
     order) when every eval module is a block activation the engine serves, else None (``why`` receives
-    the reason; an EfficientNet with ``shapley`` is rejected: ``EFFNET_SHAPLEY_REASON``). ``grad`` is accepted for
-    symmetry with the ResNet engine: the same modules are served forward (APoZ) and backward
-    (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation; where the engine cannot run,
-    a MobileNetV3 is told what its prefixes need (``V3_SHAPLEY_REASON``)."""
+    the reason). ``grad`` is accepted for symmetry with the ResNet engine: the same modules are served
+    forward (APoZ) and backward (Taylor, Sensitivity). ``shapley``: the caller wants prefix evaluation;
+    where the engine cannot run, a MobileNetV3 is told what its prefixes need (``V3_SHAPLEY_REASON``). An
+    EfficientNet's prefixes run on the engine only with ``shapley="lower"`` (the ``"shapley"`` value of the
+    ``mobilenet_engine`` option); ``shapley=True`` rejects it there: ``EFFNET_SHAPLEY_REASON``."""
     from .fused_chain import _reject, engines_enabled
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     if not engines_enabled():
@@ -1452,7 +1596,7 @@ def maybe_mobilenet_engine(model, eval_modules, device, grad=False, why=None, sh
                 return _reject(why, f"mobilenet engine: {reason_e}")
             v3 = any(isinstance(getattr(m, "block", None), nn.Sequential) for m in feats)
             return _reject(why, f"mobilenet engine: {reason3 if v3 else reason}")
-        if shapley:
+        if shapley and shapley != "lower":
             return _reject(why, EFFNET_SHAPLEY_REASON)
     new = cls(model, plan)
     eng = _ENGINES.get(model)

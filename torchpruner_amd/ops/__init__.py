@@ -17,6 +17,7 @@ from .dwconv_act import dwconv_act_dgrad, dwconv_act_fwd, dwconv_act_tay_slots
 from .dwconv_hs import dwconv_hs_dgrad, dwconv_hs_fwd, dwconv_hs_tay_slots
 from .dwconv_silu import dwconv_silu_dgrad, dwconv_silu_fwd, dwconv_silu_pool_slots, dwconv_silu_tay_slots
 from .scaled_project import scaled_project
+from .silu_prefix_project import silu_prefix_project
 from .silu_project import silu_project_dgrad, silu_project_fwd, silu_project_tay_slots
 from .se import (SE_ACTS, SE_GATES, se_bwd_dx, se_bwd_reduce, se_gate_act_bwd, se_gate_act_fwd, se_gate_bwd,
                  se_gate_fwd, se_pool, se_scale, se_wgrad)
@@ -31,7 +32,7 @@ __all__ = [
     "SE_GATES", "se_pool", "se_gate_fwd", "se_scale", "se_bwd_reduce", "se_gate_bwd", "se_bwd_dx", "se_wgrad",
     "SE_ACTS", "se_gate_act_fwd", "se_gate_act_bwd",
     "bn_hswish_fwd", "bn_hswish_bwd", "bn_silu_fwd", "bn_silu_bwd",
-    "silu_project_fwd", "silu_project_dgrad", "silu_project_tay_slots",
+    "silu_project_fwd", "silu_project_dgrad", "silu_project_tay_slots", "silu_prefix_project",
 ]
 
 REDUCE_MODES = {"taylor": 0, "taylor_signed": 1, "sensitivity": 2, "apoz": 3, "sum_grad": 4}
