@@ -35,8 +35,9 @@
 // consecutive rows (a run ends where the image does) and leaves each run's sum at the run's first row in
 // the LDS tile; then one thread per (image of the tile, channel quad) adds the run heads of its image in
 // row order (the image's first row, then every multiple of 8 inside it) and stores into slot
-// (tile - first tile of the image). An image of HW rows meets at most (HW + 62) / 64 + 1 tiles (HW / 64
-// when 64 divides HW): the slot count. A tile may hold up to 64 images (HW = 1) or a 64th of one.
+// (tile - first tile of the image). An image of HW rows meets at most (HW - g + 63) / 64 + 1 tiles,
+// g = gcd(HW, 64) (HW / 64 when 64 divides HW): the slot count. A tile may hold up to 64 images (HW = 1) or
+// a 64th of one.
 //
 // APoZ counts are integers: LDS integer atomics per (image of the tile, channel of the slice), then one
 // float atomic per non-zero count (exact up to 2^24, order-independent), as dwconv_silu.hip adds its.
@@ -322,10 +323,12 @@ static bool sj_aligned(std::initializer_list<const void*> ps) {
 
 }  // namespace tp
 
-// Slots R of the dgrad's (R, B, C) score-partial slab for images of HW rows; 0 for a rejected shape
+// Slots R of the dgrad's (R, B, C) score-partial slab for images of HW rows; 0 for a rejected shape. An image
+// starts at a multiple of g = gcd(HW, 64) inside its first tile, at 64 - g at the latest.
 extern "C" int tp_silu_project_tay_slots(int HW, int C) {
   if (HW < 1 || C < 4 || C % 4 != 0) return 0;
-  return HW % tp::SJ_BM == 0 ? HW / tp::SJ_BM : (int)(((long long)HW + tp::SJ_BM - 2) / tp::SJ_BM) + 1;
+  const int g = (HW & -HW) < tp::SJ_BM ? (HW & -HW) : tp::SJ_BM;
+  return (int)(((long long)HW - g + tp::SJ_BM - 1) / tp::SJ_BM) + 1;
 }
 
 // out (N, Co) = (silu(z) @ wt) * scale + shift (+ res): z (N, C), wt (C, Co), scale / shift (Co), res (N, Co)

@@ -13,9 +13,9 @@ C_ULP = 10
 N = 2 * 5 * 7  # two 64-row tiles, the second one partial
 
 
-def _case(C, Co, seed=0):
+def _case(C, Co, seed=0, N=N):
     """n real channels and 1 (C = 4) or 3 padding channels that rank after them."""
-    g = torch.Generator().manual_seed(seed * 10000 + C * 200 + Co)
+    g = torch.Generator().manual_seed(seed * 10000 + C * 200 + Co + (0 if N == 70 else N * 1000000))
     n = C - (1 if C == 4 else 3)
     perm = torch.randperm(n, generator=g)
     rank = torch.full((C,), n + 1)
@@ -27,7 +27,7 @@ def _case(C, Co, seed=0):
 
 def _check(cuda, t, p0, cnt, with_res, label):
     from torchpruner_amd import ops
-    C = t["z"].shape[1]
+    N, C = t["z"].shape
     cnt = min(cnt, t["perm"].numel() + 1 - p0)  # the prefixes a permutation of n channels has from p0 on
 
     def run(f, g, cnt=cnt):
@@ -52,6 +52,25 @@ def _check(cuda, t, p0, cnt, with_res, label):
 @pytest.mark.parametrize("C", [4, 36, 96])
 def test_matches_the_fp64_body(cuda, C, Co, p0, cnt, with_res):
     _check(cuda, _case(C, Co), p0, cnt, with_res, f"C={C} Co={Co}")
+
+
+# Tile edges. Co: the dispatcher's boundaries (32 | 36: one | two accumulators, 64 | 68: two | four; 36 and 64 run
+# the two-accumulator instantiation) and a partly filled four-accumulator tile (100). N: one row, fewer than 32 (the
+# second wave owns no valid row), exact multiples of 64, one past. cnt - 1 steps that fill one or two 32-step LDS
+# delta tiles exactly (32, 64), overflow them by one (33, 65), and the full scan p0 = 0, cnt = n + 1, whose last copy
+# is shift + res plus the padding channels. (p0, cnt) = (n, 1): every real channel masked in the GEMM itself.
+EDGES = [(36, Co, N, 3, 35) for Co in (32, 36, 64, 68, 100)]
+EDGES += [(36, 40, rows, 3, 35) for rows in (1, 31, 64, 65, 128)]
+EDGES += [(96, 40, N, 0, cnt) for cnt in (33, 34, 65, 66, 94)]
+EDGES += [(C, 24, N, C - (1 if C == 4 else 3), 1) for C in (4, 36, 96)]
+
+
+@pytest.mark.parametrize("C,Co,rows,p0,cnt", EDGES)
+def test_tile_edges_match_the_fp64_body(cuda, C, Co, rows, p0, cnt):
+    t = _case(C, Co, N=rows)
+    n = t["perm"].numel()
+    assert p0 + cnt - 1 <= n or (p0, cnt) == (3, 35)  # only the 35 is clamped (to n - 2 copies from p0 = 3)
+    _check(cuda, t, p0, cnt, True, f"edges N={rows} C={C} Co={Co}")
 
 
 def test_extreme_pre_activations_stay_finite_and_inside_the_bound(cuda):

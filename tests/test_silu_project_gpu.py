@@ -16,6 +16,12 @@ C_ULP = 33
 # C: one partial K slice, two, four (two column chunks of the dgrad). Co: one, two, four (72, 128) accumulators.
 SHAPES = list(itertools.product([(1, 1), (5, 9), (2, 49), (3, 150)], [4, 36, 100], [4, 24, 40]))
 SHAPES += [((3, 150), 100, 72), ((70, 1), 36, 128)]
+# Tile edges. Co at the forward dispatcher's boundaries (32 | 36, 64 | 68) and a partly filled four-accumulator
+# tile (100); C of exactly two and four K slices / one and two dgrad column chunks, and one column past them (132);
+# HW a multiple of 64 (the slot formula's other branch, no image shares a tile), 63 and 65 around it, 32 (two images
+# fill a tile exactly).
+SHAPES += [((2, 49), 36, Co) for Co in (32, 64, 68, 100)] + [((2, 49), C, 24) for C in (64, 128, 132)]
+SHAPES += [(shape, 36, 24) for shape in ((2, 64), (2, 128), (3, 63), (3, 65), (2, 32))]
 _CASES = {}
 
 

@@ -221,6 +221,7 @@ HOST_PROGRAMS = {
     "se_validation": ("squeeze_excite",),
     "bn_hswish_validation": ("batchnorm",),
     "prefix_project_validation": ("prefix_project",),
+    "project_gemm_validation": ("scaled_project", "silu_project", "silu_prefix_project"),
     "conv2x2_fast_validation": ("conv_mfma", "conv2x2_fast"),
     "elementwise_validation": ("channel_reduce", "prune_ops", "shapley", "train_ops", "data_ops"),
 }

@@ -30,10 +30,10 @@ def _silu_both(z: torch.Tensor):
 
 def silu_project_tay_slots(hw: int, C: int) -> int:
     """Slots R of :func:`silu_project_dgrad`'s (R, B, C) slab for images of ``hw`` rows: the 64-row tiles an
-    image can meet; 0 for a rejected shape."""
+    image can meet (it starts at a multiple of g = gcd(hw, 64) inside its first tile); 0 for a rejected shape."""
     if hw < 1 or C < 4 or C % 4:
         return 0
-    return hw // 64 if hw % 64 == 0 else (hw + 62) // 64 + 1
+    return (hw - min(hw & -hw, 64) + 63) // 64 + 1
 
 
 def _check(N, C, Co, what):
